@@ -2,7 +2,7 @@
 """Headline benchmark (BASELINE.json): rows/s of hash-groupby SUM+COUNT over 1B int64-key / float64-value rows
 with 1M groups (configs[1], "C2"), one process per GPU.
 
-  python bench.py --gpus 1 --steps K --warmup W
+  python bench.py --gpus 1 --steps K --warmup W [--dump-outputs DIR]
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N --steps K --warmup W
 
 A step = one pass of the hot path over one batch of synthetic rows already resident in HBM:
@@ -64,7 +64,16 @@ def parse():
                          "headline line otherwise carries in `hash_table_variant`, `two_value_columns_variant` and `secondary`")
     ap.add_argument("--variant-steps", type=int, default=5)
     ap.add_argument("--cpu-sample-rows", type=int, default=60_000_000)
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write what the last timed step returned (the output keys, SUM and COUNT_VALID, one row "
+                         "per group in key order) as DIR/<name>.npy in float64, at most 64 MB in all (a fixed seeded sample of the groups "
+                         "beyond that), so that two builds can be compared output for output. Single-GPU C2 only.")
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.dump_outputs and (args.config != "c2" or args.gpus != 1):
+        ap.error("--dump-outputs covers the single-GPU C2 path (--config c2 --gpus 1)")
+    return args
 
 
 def cpu_baseline(groups, sample_rows):
@@ -241,6 +250,29 @@ def _timeit(fn):
     return time.perf_counter() - t0
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, keys, columns):
+    """Writes `keys` and each of `columns` (name -> device tensor, one row per group) as out_dir/<name>.npy in float64, rows in key
+    order: the order of a groupby's output rows is unspecified, so this is what makes two runs comparable file by file. Beyond
+    DUMP_LIMIT_BYTES in all, the same seeded sample of row positions in key order is written for every array.
+    Returns (groups, rows written)."""
+    import numpy as np
+    import torch
+    columns = {"keys": keys, **columns}
+    order = torch.argsort(keys)
+    groups = order.numel()
+    fit = (DUMP_LIMIT_BYTES - 4096) // (8 * len(columns))  # (4 KB for the .npy headers)
+    if groups > fit:
+        pick = np.sort(np.random.default_rng(0).choice(groups, fit, replace=False))
+        order = order[torch.from_numpy(pick).to(order.device)]
+    os.makedirs(out_dir, exist_ok=True)
+    for name, col in columns.items():
+        np.save(os.path.join(out_dir, f"{name}.npy"), col[order].to(torch.float64).cpu().numpy())
+    return groups, order.numel()
+
+
 def main():
     args = parse()
     # Libraries print banners on the C-level stdout (RCCL: "RCCL version : ...", "Hostname : ..."): everything but the
@@ -276,6 +308,8 @@ def main():
     stream = torch.cuda.current_stream()
 
     force_dist = os.environ.get("BENCH_FORCE_DISTRIBUTED") == "1"  # rehearse the N>1 code path on one GPU
+    if force_dist and args.dump_outputs:
+        sys.exit("--dump-outputs covers the single-GPU C2 path, not BENCH_FORCE_DISTRIBUTED=1")
     # N > 1: `value` is the LITERAL config-5 form, inside the library (cudf::distributed::shuffle_groupby: hash-range partition of
     # the rows -> RCCL Send/Recv -> per-GPU groupby); the combiner form is timed in the same run and reported beside it.
     # BENCH_DIST_MODE = shuffle_native (default) | shuffle (the same through torch.distributed) | preaggregate (combiner as `value`)
@@ -388,6 +422,13 @@ def main():
             del ref_c, ref_s, gc, gs, err
         except Exception as e:  # noqa: BLE001
             result_check = {"error": repr(e)}
+
+    if args.dump_outputs:
+        rkeys, rres = last[1]
+        res = rres[0].columns()
+        groups_out, written = dump_outputs(args.dump_outputs, rkeys.columns()[0].to_torch(),
+                                           {"sum": res[0].to_torch(), "count_valid": res[1].to_torch()})
+        sys.stderr.write(f"[bench] --dump-outputs: {written} of {groups_out} groups written to {args.dump_outputs}\n")
 
     # ---- N == 1, after the primary timed region: the other side of the cliffs next to the headline, in the driver's own record.
     # hash_table_variant: the same rows with every key multiplied by an odd constant (a bijection: same groups, same counts, but
