@@ -1,5 +1,5 @@
-"""Dense-key path (direct-address tables, chunked through the Infinity Cache): parity against torch reductions at sizes
-that exercise one and several chunks, then a chunk-size sweep of the C2 call.
+"""Dense-key path (direct-address tables): parity against torch reductions at a few sizes and key ranges, then the C2 call with
+the dense path on and off.
   python bench_micro/dense_check.py [rows]"""
 import os
 import sys
@@ -71,17 +71,15 @@ def bench(n, groups, steps=5):
 
 if __name__ == "__main__":
     rows = int(sys.argv[1]) if len(sys.argv) > 1 else 1_000_000_000
-    check(5_000_000, 1_000_000, label="one chunk")
-    check(30_000_000, 1_000_000, lo=-123456789, label="three chunks, negative keys")
+    check(5_000_000, 1_000_000, label="5M rows")
+    check(30_000_000, 1_000_000, lo=-123456789, label="30M rows, negative keys")
     check(30_000_000, 200_000, lo=10**15, dtype=torch.int64, label="int64 values")
     check(30_000_000, 3_000_000, label="3M keys")
     os.environ["CUDF_AMD_GB_DENSE"] = "0"
     check(30_000_000, 1_000_000, label="dense off")
     os.environ["CUDF_AMD_GB_DENSE"] = "1"
-    for q in (2, 4, 6, 8, 12, 16, 24, 1000):
-        os.environ["CUDF_AMD_GB_CHUNK_ROWS"] = str(q * 256 * 5120)
-        ms, path = bench(rows, 1_000_000)
-        print(f"C2 rows={rows} chunk={q}x1.31M rows: {ms:.2f} ms/step path={path}", flush=True)
+    ms, path = bench(rows, 1_000_000)
+    print(f"C2 rows={rows}: {ms:.2f} ms/step path={path}", flush=True)
     os.environ["CUDF_AMD_GB_DENSE"] = "0"
     ms, path = bench(rows, 1_000_000)
     print(f"C2 rows={rows} dense off: {ms:.2f} ms/step path={path}", flush=True)

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """C3's shape (500M x 50M rows, selectivity 0.3, unique build tuples) with keys the partitioned joins did not take before round 4:
-one float64 column, (int64, int64), (int64, int32). Default against CUDF_AMD_JOIN_RADIX=0 (the open-addressing table in HBM) - run twice,
-once per setting: the switch is read per join object. Usage: python bench_micro/join_key_shapes.py [scale]"""
+one float64 column, (int64, int64), (int64, int32). Default against the open-addressing table in HBM (CUDF_AMD_JOIN_RADIX_MIN_BUILD
+above the build size) - run twice, once per setting: the setting is read per join object. Usage: python bench_micro/join_key_shapes.py [scale]"""
 import json, os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
@@ -34,7 +34,10 @@ def shapes():
 for name, lcols, rcols in shapes():
     L, R = cudf_amd.Table(lcols), cudf_amd.Table(rcols)
     for radix in ("1", "0"):
-        os.environ["CUDF_AMD_JOIN_RADIX"] = radix
+        if radix == "1":
+            os.environ.pop("CUDF_AMD_JOIN_RADIX_MIN_BUILD", None)
+        else:
+            os.environ["CUDF_AMD_JOIN_RADIX_MIN_BUILD"] = str(nr + 1)
         J.inner_join(L, R, NullEquality.EQUAL)
         torch.cuda.synchronize()
         _lib.profile_reset(); _lib.profile_enable(True)

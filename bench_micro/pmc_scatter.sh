@@ -4,7 +4,6 @@ ROOT=${GRAFT_REPO_ROOT:-$PWD}
 OUT=$ROOT/gpurun_out/pmcs
 rm -rf $OUT && mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
-export CUDF_AMD_GB_CHUNKED=0
 for SET in "SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_LDS SQ_WAIT_INST_LDS" "SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_INSTS_VMEM_RD SQ_INSTS_VMEM_WR SQ_ACTIVE_INST_VMEM SQ_ACTIVE_INST_SCA SQ_LDS_BANK_CONFLICT"; do
   tag=$(echo $SET | cut -c1-12 | tr ' ' '_')
   timeout -k 10 300 rocprofv3 --kernel-trace --pmc $SET --output-format csv -d $OUT -o $tag -- python3 $ROOT/bench.py --steps 2 --warmup 1 --no-cpu-baseline > $OUT/log_$tag.txt 2>&1

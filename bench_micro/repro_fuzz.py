@@ -70,7 +70,7 @@ for vals, kinds in requests:
     for k in kinds:
         run([(vals, [k])], f"alone: {k}")
 run([(vals, ["count_valid", "count_all", "sum"]) for vals, _ in requests], "count_valid+count_all+sum")
-for var, val in (("CUDF_AMD_GB_EXACT", "1"), ("CUDF_AMD_GB_P", "256"), ("CUDF_AMD_GB_LDS_KB", "64")):
+for var, val in (("CUDF_AMD_GB_LDS_KB", "64"),):
     os.environ[var] = val
     run(requests, f"{var}={val}")
     del os.environ[var]

@@ -4,6 +4,7 @@
 // (hash_partition -> pack -> shuffle -> unpack); the split itself restates partitioning.cu:187-337 (histogram, scan,
 // LDS-staged scatter) for a handful of destinations and 64-lane waves.
 #include "../common/device_table.hpp"
+#include "../common/env.hpp"
 #include "../common/profiler.hpp"
 
 #include <cudf/distributed.hpp>
@@ -162,12 +163,8 @@ struct loopback_hub {
   }
   static long barrier_timeout_s()
   {
-    static long const v = [] {
-      char const* e = std::getenv("CUDF_AMD_LOOPBACK_TIMEOUT_S");
-      long const x  = e != nullptr ? std::atol(e) : 0;
-      return x > 0 ? x : 120L;
-    }();
-    return v;
+    int64_t const x = cudf::detail::env_i64("CUDF_AMD_LOOPBACK_TIMEOUT_S", 0);
+    return x > 0 ? static_cast<long>(x) : 120L;
   }
 };
 class loopback_transport final : public transport {
@@ -739,13 +736,9 @@ std::unique_ptr<table> shuffle_body(table_view const& input, std::vector<size_ty
   // ---- local split by owner rank
   auto f = flatten(input, with_validity, s);
   // (the columns are scattered one per launch on a side stream: the count exchange below and the payload rounds of column c run
-  // beside the scatter of the columns after c. CUDF_AMD_SHUFFLE_PIPELINE=0: one fused scatter on the caller's stream.)
-  static bool const pipelined = [] {
-    char const* e = std::getenv("CUDF_AMD_SHUFFLE_PIPELINE");
-    return e == nullptr || std::atoi(e) != 0;
-  }();
+  // beside the scatter of the columns after c; one column takes one fused scatter on the caller's stream.)
   scatter_pipeline pipe;  // (partition_flat returns with `s` waiting for the last column's event: buffers released on `s` are safe)
-  if (pipelined && f.cols.size() > 1) pipe.open(f.cols.size());
+  if (f.cols.size() > 1) pipe.open(f.cols.size());
   auto [bufs, off] = partition_flat(f, hashed, N, stream, tmp, pipe.side != nullptr ? &pipe : nullptr);
 
   // ---- counts: every rank learns what every rank sends to every rank

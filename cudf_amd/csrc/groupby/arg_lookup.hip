@@ -195,8 +195,7 @@ std::optional<std::pair<std::unique_ptr<table>, std::vector<aggregation_result>>
   if (kcls != CLS_SINT && kcls != CLS_UINT && kcls != CLS_BOOL) return std::nullopt;
   // (the switches are read per call: the test suite flips them between calls of one process)
   planner_env const env = planner_env::load();
-  char const* const sw  = std::getenv("CUDF_AMD_GB_ARG_LOOKUP");
-  if ((sw != nullptr && std::atoi(sw) == 0) || n < env.big_min_rows) return std::nullopt;
+  if (!env.arg_lookup || n < env.big_min_rows) return std::nullopt;
 
   hipStream_t const s = stream.value();
   auto tmp            = get_current_device_resource_ref();

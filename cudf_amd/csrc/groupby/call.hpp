@@ -99,12 +99,9 @@ namespace cudf::groupby::detail {
 // Every switch of the planner. Read ONCE per call - a call never sees two values of one switch - and not
 // once per process: the test suite flips them between calls of one process (forced paths, shrunken tables).
 struct planner_env {
-  int64_t lds_kb, agg_block, big_min_rows, estimate_min_rows, forced_p, s_items, preagg_min_pct, dense_log2p, scatter_block, rpt;
-  int64_t one_table_min_rows, sample_div;
-  int64_t dense_nsplit, wc_g, slices, plan_load_pct;  // -1: not set (the default depends on the plan)
-  bool dense, dense_composite, dense_one_table, dense_ring, dense_multi, hot, preagg, optimistic, optimistic2, exact, wc, cyclic,
-    stamps, debug, no_simple, vec16, trace, collapse_runs;
-  int64_t static_shapes;  // composite dense keys: 0 = run-time loader, 1 / 2 = compiled column shapes with one / two tiles of loads in flight
+  int64_t lds_kb, big_min_rows, one_table_min_rows, dense_log2p;
+  int64_t dense_nsplit;  // -1: not set (the default depends on the plan)
+  bool dense, dense_one_table, dense_ring, dense_multi, preagg, optimistic2, collapse_runs, arg_lookup, debug, trace;
   static planner_env load();
 };
 
@@ -130,7 +127,7 @@ struct host_plan {
   int keynulls_unit{-1}, keynulls_hi{0};
 };
 
-host_plan build_plan(table_view const& keys, null_policy policy, std::span<aggregation_request const> requests, planner_env const& env);
+host_plan build_plan(table_view const& keys, null_policy policy, std::span<aggregation_request const> requests);
 // Heavy-hitter handling covers plans whose accumulators are SUMs of the single value column and row COUNTs (no nulls).
 bool hot_plan_ok(plan_dev const& p);
 bool is_engine_kind(aggregation::Kind k);

@@ -109,7 +109,7 @@ __global__ void __launch_bounds__(256) k_key_ranges(plan_dev const* __restrict__
 
 // ------------------------------------------------------------------ K_aggregate_dense
 // LDS image of a table: accumulator q as [slots] u64 (u32 for a COUNT), 8-byte arrays first; then the occupancy bitmap
-// [slots / 32] u32 if no accumulator counts every row. The image is copied verbatim from / to HBM between chunks.
+// [slots / 32] u32 if no accumulator counts every row. The image is copied verbatim to HBM when several images are merged.
 struct dense_layout {
   uint32_t off[MAX_ACC];
   uint32_t occ_off;
@@ -137,7 +137,7 @@ __host__ __device__ inline dense_layout make_dense_layout(plan_dev const& p, int
 
 // SIG: compile-time accumulator signature (device_common.hpp), 0 = descriptors read at run time.
 // One workgroup per partition; wave w walks the regions [w * g, (w + 1) * g) of its partition as ONE virtual record range
-// (a chunk's regions hold 50-400 records each: walked one by one they would be all tail).
+// (a partition's regions hold 50-400 records each: walked one by one they would be all tail).
 // The key units of the partial record of dense index `idx` (what k_finalize reads): a single plain key is lo + idx; composite
 // keys are rebuilt from the mixed-radix digits of the index and placed where the plan's key units hold them.
 __device__ __forceinline__ void dense_store_key_units(dense_map const& m, int KU, uint32_t idx, uint64_t* o)
@@ -163,7 +163,7 @@ __device__ __forceinline__ void dense_store_key_units(dense_map const& m, int KU
 
 // SOA: 10-byte records of the ring scatter (value stream + 16-bit tag stream) instead of 16-byte {key | value} records.
 template <uint64_t SIG, int NACCT, bool SOA>
-__global__ void __launch_bounds__(1024, 8) k_aggregate_dense(dense_agg_args const* __restrict__ ap, int first_chunk, int last_chunk)
+__global__ void __launch_bounds__(1024, 8) k_aggregate_dense(dense_agg_args const* __restrict__ ap)
 {
   extern __shared__ __attribute__((aligned(16))) unsigned char lds_raw[];
   __shared__ uint32_t s_dump;
@@ -199,25 +199,19 @@ __global__ void __launch_bounds__(1024, 8) k_aggregate_dense(dense_agg_args cons
   auto acc64 = [&](int q) { return reinterpret_cast<uint64_t*>(lds_raw + acc_off[q]); };
   auto acc32 = [&](int q) { return reinterpret_cast<uint32_t*>(lds_raw + acc_off[q]); };
 
-  // ---- table: identities on the first chunk, the carried image afterwards
-  uint64_t* image = a.tables + static_cast<int64_t>(blockIdx.x) * (a.image_bytes / 8);
-  if (first_chunk) {
+  // ---- table: identities
 #pragma unroll
-    for (int q = 0; q < NACCT; ++q) {
-      if (q >= NACC) break;
-      if (acc_narrow[q]) {
-        for (int s = threadIdx.x; s < slots; s += B) acc32(q)[s] = 0;
-      } else {
-        uint64_t const id = acc_identity(acc_op[q]);
-        for (int s = threadIdx.x; s < slots; s += B) acc64(q)[s] = id;
-      }
+  for (int q = 0; q < NACCT; ++q) {
+    if (q >= NACC) break;
+    if (acc_narrow[q]) {
+      for (int s = threadIdx.x; s < slots; s += B) acc32(q)[s] = 0;
+    } else {
+      uint64_t const id = acc_identity(acc_op[q]);
+      for (int s = threadIdx.x; s < slots; s += B) acc64(q)[s] = id;
     }
-    if (occ_acc < 0)
-      for (int s = threadIdx.x; s < (slots + 31) / 32; s += B) occ[s] = 0;
-  } else {
-    for (int i = threadIdx.x; i < a.image_bytes / 16; i += B)
-      reinterpret_cast<u64x2*>(lds_raw)[i] = gload(reinterpret_cast<u64x2 const*>(image) + i);
   }
+  if (occ_acc < 0)
+    for (int s = threadIdx.x; s < (slots + 31) / 32; s += B) occ[s] = 0;
   if (threadIdx.x == 0) s_dump = 0;
   __syncthreads();
 
@@ -346,12 +340,13 @@ __global__ void __launch_bounds__(1024, 8) k_aggregate_dense(dense_agg_args cons
     }
   }
   __syncthreads();
-  if (!last_chunk || nsplit > 1 || a.keep_images) {  // the image is carried to the next chunk, or merged with the partition's other shares / columns
+  if (nsplit > 1 || a.keep_images) {  // the image is merged with the partition's other shares / columns
+    uint64_t* image = a.tables + static_cast<int64_t>(blockIdx.x) * (a.image_bytes / 8);
     for (int i = threadIdx.x; i < a.image_bytes / 16; i += B)
       gstore(reinterpret_cast<u64x2*>(image) + i, reinterpret_cast<u64x2 const*>(lds_raw)[i]);
     return;
   }
-  // ---- last chunk: occupied slots -> partial records [key units | accumulators] (k_finalize reads them)
+  // ---- occupied slots -> partial records [key units | accumulators] (k_finalize reads them)
   int const KU       = a.KU;
   int const PU       = KU + NACC;
   uint64_t* out      = a.out_records + static_cast<int64_t>(item) * slots * PU;
@@ -509,20 +504,19 @@ void store_args(dense_agg_args const& a, dense_agg_args* d_args, hipStream_t str
 }
 
 template <uint64_t SIG, int NACCT, bool SOA>
-static void launch_dense_t(dense_agg_args const& a, dense_agg_args const* d_args, bool first_chunk, bool last_chunk, hipStream_t stream)
+static void launch_dense_t(dense_agg_args const& a, dense_agg_args const* d_args, hipStream_t stream)
 {
   static std::once_flag attr_once;  // (the API is re-entrant across objects: two threads may launch this kernel first)
   std::call_once(attr_once, [] { allow_full_lds(reinterpret_cast<void const*>(&k_aggregate_dense<SIG, NACCT, SOA>)); });
   cudf::detail::prof::scope prof_{"aggregate", stream};
-  hipLaunchKernelGGL((k_aggregate_dense<SIG, NACCT, SOA>), dim3(a.nitems * std::max(a.nsplit, 1)), dim3(a.block), a.image_bytes, stream, d_args,
-                     first_chunk ? 1 : 0, last_chunk ? 1 : 0);
+  hipLaunchKernelGGL((k_aggregate_dense<SIG, NACCT, SOA>), dim3(a.nitems * std::max(a.nsplit, 1)), dim3(a.block), a.image_bytes, stream, d_args);
   CUDF_HIP_TRY(hipGetLastError());
 }
 template <uint64_t SIG, int NACCT>
-static void launch_dense_n(dense_agg_args const& a, dense_agg_args const* d_args, bool first_chunk, bool last_chunk, hipStream_t stream)
+static void launch_dense_n(dense_agg_args const& a, dense_agg_args const* d_args, hipStream_t stream)
 {
-  if (a.rec_tag != nullptr) return launch_dense_t<SIG, NACCT, true>(a, d_args, first_chunk, last_chunk, stream);
-  return launch_dense_t<SIG, NACCT, false>(a, d_args, first_chunk, last_chunk, stream);
+  if (a.rec_tag != nullptr) return launch_dense_t<SIG, NACCT, true>(a, d_args, stream);
+  return launch_dense_t<SIG, NACCT, false>(a, d_args, stream);
 }
 
 void launch_dense_merge_dump_wide(dense_agg_args const& a, dense_agg_args const* d_args, hipStream_t stream)
@@ -543,7 +537,7 @@ void launch_dense_merge_dump(dense_agg_args const& a, dense_agg_args const* d_ar
   CUDF_HIP_TRY(hipGetLastError());
 }
 
-void launch_aggregate_dense(dense_agg_args const& a, dense_agg_args const* d_args, bool first_chunk, bool last_chunk, hipStream_t stream)
+void launch_aggregate_dense(dense_agg_args const& a, dense_agg_args const* d_args, hipStream_t stream)
 {
   CUDF_EXPECTS(a.plan.narg == 0 && (a.map.nkeys > 0 || (a.plan.simple && a.plan.KU == 1 && a.plan.NPAY == 1)),
                "dense keys: one plain key column and one plain value column, or composite integer keys and one value column");
@@ -552,17 +546,17 @@ void launch_aggregate_dense(dense_agg_args const& a, dense_agg_args const* d_arg
                  a.occ_acc == dense_occ_acc(a.plan) && a.image_bytes == static_cast<int32_t>(dense_table_bytes(a.plan, a.slots)),
                "dense keys: table geometry");
   uint64_t const sig = plan_sig(a.plan);
-  if (sig == SIG_SUMF_CNT) return launch_dense_n<SIG_SUMF_CNT, 2>(a, d_args, first_chunk, last_chunk, stream);
-  if (sig == SIG_SUMI_CNT) return launch_dense_n<SIG_SUMI_CNT, 2>(a, d_args, first_chunk, last_chunk, stream);
-  if (sig == SIG_SUMF) return launch_dense_n<SIG_SUMF, 2>(a, d_args, first_chunk, last_chunk, stream);
-  if (sig == SIG_SUMI) return launch_dense_n<SIG_SUMI, 2>(a, d_args, first_chunk, last_chunk, stream);
-  if (sig == SIG_CNT) return launch_dense_n<SIG_CNT, 2>(a, d_args, first_chunk, last_chunk, stream);
-  if (sig == SIG_MEAN_MIN_MAX_F) return launch_dense_n<SIG_MEAN_MIN_MAX_F, 4>(a, d_args, first_chunk, last_chunk, stream);
-  if (sig == SIG_MEAN_MIN_MAX_F_NULLS) return launch_dense_n<SIG_MEAN_MIN_MAX_F_NULLS, 4>(a, d_args, first_chunk, last_chunk, stream);
-  if (sig == SIG_SUMF_CNT_NULLS) return launch_dense_n<SIG_SUMF_CNT_NULLS, 2>(a, d_args, first_chunk, last_chunk, stream);
-  if (sig == SIG_SUMI_CNT_NULLS) return launch_dense_n<SIG_SUMI_CNT_NULLS, 2>(a, d_args, first_chunk, last_chunk, stream);
-  if (a.plan.NACC <= 4) return launch_dense_n<0, 4>(a, d_args, first_chunk, last_chunk, stream);
-  return launch_dense_n<0, MAX_ACC>(a, d_args, first_chunk, last_chunk, stream);
+  if (sig == SIG_SUMF_CNT) return launch_dense_n<SIG_SUMF_CNT, 2>(a, d_args, stream);
+  if (sig == SIG_SUMI_CNT) return launch_dense_n<SIG_SUMI_CNT, 2>(a, d_args, stream);
+  if (sig == SIG_SUMF) return launch_dense_n<SIG_SUMF, 2>(a, d_args, stream);
+  if (sig == SIG_SUMI) return launch_dense_n<SIG_SUMI, 2>(a, d_args, stream);
+  if (sig == SIG_CNT) return launch_dense_n<SIG_CNT, 2>(a, d_args, stream);
+  if (sig == SIG_MEAN_MIN_MAX_F) return launch_dense_n<SIG_MEAN_MIN_MAX_F, 4>(a, d_args, stream);
+  if (sig == SIG_MEAN_MIN_MAX_F_NULLS) return launch_dense_n<SIG_MEAN_MIN_MAX_F_NULLS, 4>(a, d_args, stream);
+  if (sig == SIG_SUMF_CNT_NULLS) return launch_dense_n<SIG_SUMF_CNT_NULLS, 2>(a, d_args, stream);
+  if (sig == SIG_SUMI_CNT_NULLS) return launch_dense_n<SIG_SUMI_CNT_NULLS, 2>(a, d_args, stream);
+  if (a.plan.NACC <= 4) return launch_dense_n<0, 4>(a, d_args, stream);
+  return launch_dense_n<0, MAX_ACC>(a, d_args, stream);
 }
 
 void launch_key_ranges(plan_dev const* d_plan, int nkeycols, int64_t nrows, int64_t sample, int64_t* out, hipStream_t stream)

@@ -349,9 +349,9 @@ bool try_static_shape(dense_ring_args const& a, dense_ring_args const* d_args, h
   // Two tiles of loads in flight where the shape's registers allow it (one key column: 106-123 VGPRs, no scratch; 1B rows on 1M
   // groups, int32 key 7.9 -> 6.3 ms, int64 key with a nullable value 8.1 -> 7.2 ms). Two key columns with masks (C4's shape) spill
   // 32-48 bytes with two tiles and run no faster than the run-time loader (13.6 ms); with one tile C4's first level takes 6.06
-  // instead of 7.2 ms (profiles/r3_c4_static_ab.txt). CUDF_AMD_GB_STATIC_SHAPES=1 forces one tile, 0 the run-time loader.
+  // instead of 7.2 ms (profiles/r3_c4_static_ab.txt).
   constexpr bool WIDE = SHAPE::W1 != 0 && (SHAPE::M0 || SHAPE::M1);
-  if (WIDE || a.static_shapes == 1) launch_ring_t<RING_SRC_COLS_STATIC, 4, 1, SHAPE>(a, d_args, stream);
+  if constexpr (WIDE) launch_ring_t<RING_SRC_COLS_STATIC, 4, 1, SHAPE>(a, d_args, stream);
   else launch_ring_t<RING_SRC_COLS_STATIC, 4, STATIC_TILES_AHEAD, SHAPE>(a, d_args, stream);
   return true;
 }
@@ -374,10 +374,9 @@ void launch_dense_ring_scatter(dense_ring_args const& a, dense_ring_args const* 
     // (composite loader: 4 rows per thread, one tile ahead. Measured on C4's first level: two tiles ahead spill - 14.3 ms against
     // 9.4 - and 2 or 3 rows per thread with two or three tiles ahead take 11.3-13.1 ms: the per-tile barriers and flush do not amortise)
     if (a.map.nkeys > 0) {
-      if (a.static_shapes &&
-          (try_static_shape<shape_c4>(a, d_args, stream) || try_static_shape<shape_k32>(a, d_args, stream) ||
-           try_static_shape<shape_k32_vnull>(a, d_args, stream) || try_static_shape<shape_k64_vnull>(a, d_args, stream) ||
-           try_static_shape<shape_k64_k32>(a, d_args, stream)))
+      if (try_static_shape<shape_c4>(a, d_args, stream) || try_static_shape<shape_k32>(a, d_args, stream) ||
+          try_static_shape<shape_k32_vnull>(a, d_args, stream) || try_static_shape<shape_k64_vnull>(a, d_args, stream) ||
+          try_static_shape<shape_k64_k32>(a, d_args, stream))
         return;
       return launch_ring_t<RING_SRC_COLS, 4, 1>(a, d_args, stream);
     }

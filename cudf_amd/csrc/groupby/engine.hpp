@@ -98,7 +98,6 @@ struct plan_dev {
   // Fast path: every record unit is an 8-byte column without nulls that needs no conversion or normalisation
   // (int64/uint64/float64 values, 8-byte integer keys): unit u of row r is simple_base[u][r].
   int32_t simple;
-  int32_t simple_vec16;  // every simple_base pointer is 16-byte aligned: rows can be loaded two at a time (dwordx4)
   uint64_t const* simple_base[MAX_UNITS];
 };
 
@@ -245,9 +244,6 @@ struct part_args {
   // Write-combining scatter (optimistic, 16-byte records): records per output granule (4 = 64 B, 8 = 128 B); every
   // global store of the tile loop is a whole, aligned granule; 0 = classic run-per-tile scatter.
   int32_t wc_granule;
-  // Write-combining scatter of the input columns: workgroup w takes row tiles w, w + slices, ... instead of one contiguous
-  // chunk, so that sorted / clustered keys spread over every workgroup's regions as uniform ones do.
-  int32_t cyclic_tiles;
   // Heavy hitters (write-combining scatter of plain 16-byte records only): rows whose key is one of hot_keys[0..hot_n)
   // are aggregated (SUM of the value, row COUNT) in an LDS table of HOT_SLOTS entries placed hot_lds_offset bytes into
   // the workgroup's LDS instead of being scattered; workgroup w writes its non-empty entries as partial records to
@@ -257,25 +253,16 @@ struct part_args {
   uint64_t const* hot_keys;
   uint64_t* hot_out;
   int32_t* hot_count;
-  // diagnostics (CUDF_AMD_GB_STAMPS=1): per-workgroup cycle totals of the tile phases, 8 x u64 per workgroup
-  unsigned long long* stamps;
   // Dense integer keys (write-combining scatter of plain 16-byte records): partition digit from the dense map; a key
   // outside [lo, lo + range) raises bit 2 of *overflow (the sampled range was wrong: the caller redoes the call by hash).
   int32_t use_dense;
   dense_map dense;
 };
 
-// Chunked pipeline: the input rows are partitioned one CHUNK at a time into a reused ring of regions
-// that stays resident in the 256 MiB Infinity Cache, and each chunk is aggregated before the next one overwrites it.
-// A chunk's row range is a by-value kernel parameter (the device-resident part_args stay as they are).
-struct chunk_range {
-  int64_t begin, end;  // rows [begin, end) of the input columns; end == 0: all rows (no chunking)
-};
-
 // Aggregation of dense-key records into direct-address LDS tables (dense_kernels.hip). Work item d = partition d reads the
-// regions (d, w), w < slices, of an optimistic scatter. The table IMAGE (the accumulator arrays as they lie in LDS) of
-// every partition is carried across the chunks of a call in `tables`; the last chunk dumps partial records
-// [key | accumulators] for k_finalize: item d at out_records[d * slots * PU ...], count in out_count[d].
+// regions (d, w), w < slices, of an optimistic scatter, and dumps partial records [key | accumulators] for k_finalize: item d
+// at out_records[d * slots * PU ...], count in out_count[d] - or leaves its table IMAGE (the accumulator arrays as they lie in
+// LDS) in `tables` for a merge (nsplit, keep_images).
 struct dense_agg_args {
   plan_dev plan;
   dense_map map;
@@ -309,7 +296,7 @@ struct dense_agg_args {
 };
 std::size_t dense_table_bytes(plan_dev const& plan, int slots);  // LDS image of one table (multiple of 16)
 int dense_occ_acc(plan_dev const& plan);                          // dense_agg_args::occ_acc of a plan
-void launch_aggregate_dense(dense_agg_args const& a, dense_agg_args const* d_args, bool first_chunk, bool last_chunk, hipStream_t stream);
+void launch_aggregate_dense(dense_agg_args const& a, dense_agg_args const* d_args, hipStream_t stream);
 void store_args(dense_agg_args const& a, dense_agg_args* d_args, hipStream_t stream);
 // nsplit > 1: the nsplit table images of every partition -> partial records. Work item (d, j), j < dsplit, dumps the slots
 // [j * slots / dsplit, (j + 1) * slots / dsplit) of partition d to out_records[(d * dsplit + j) * (slots / dsplit) * PU ...], count in
@@ -352,7 +339,6 @@ struct dense_ring_args {
   int32_t* region_count;
   int32_t* overflow;   // bit 0: a region overflowed; bit 2: a key outside the dense range
   uint32_t const* ones;  // composite keys: one all-ones word, read in place of the validity word of a column without a mask
-  int32_t static_shapes; // composite keys: take the loader compiled for the columns' shape where there is one (CUDF_AMD_GB_STATIC_SHAPES)
   // Heavy hitters (one plain key, SUM / COUNT plans: hot_plan_ok): rows whose key is one of hot_keys[0 .. hot_n) are aggregated
   // (SUM of the value, row COUNT) in an LDS table of HOT_SLOTS entries behind the rings and never scattered; workgroup w writes
   // its non-empty entries as partial records [key | accumulators in plan order] to hot_out[w * HOT_SLOTS ...], their number to
@@ -432,7 +418,7 @@ void launch_key_ranges(plan_dev const* d_plan, int nkeycols, int64_t nrows, int6
 void store_args(part_args const& a, part_args* d_args, hipStream_t stream);
 void launch_partition_hist(part_args const& a, part_args const* d_args, hipStream_t stream);
 void launch_partition_scan(part_args const& a, part_args const* d_args, hipStream_t stream);
-void launch_partition_scatter(part_args const& a, part_args const* d_args, hipStream_t stream, chunk_range chunk = {0, 0});
+void launch_partition_scatter(part_args const& a, part_args const* d_args, hipStream_t stream);
 void launch_aggregate(agg_args const& a, agg_args* d_args, hipStream_t stream);
 // Gathers `total` groups (items' partial records, prefix[] = exclusive scan of the item counts) into the
 // typed output columns.
@@ -491,9 +477,8 @@ std::size_t aggregate_lds_bytes(plan_dev const& plan, agg_geom const& g);
 // LDS bytes of one table slot: key units, accumulators (4 bytes for counts), state word
 int aggregate_slot_bytes(plan_dev const& plan);
 std::size_t partition_lds_bytes(plan_dev const& plan, part_geom const& g);
-// write-combining scatter: can records of U units be partitioned P ways with granules of G records?
-// (block = 512: two workgroups per CU, each within 80 KiB)
-bool partition_wc_fits(int U, int P, int G, int block = 1024);
+// write-combining scatter (1024-thread workgroups): can records of U units be partitioned P ways with granules of G records?
+bool partition_wc_fits(int U, int P, int G);
 // LDS bytes of the heavy-hitter table; byte offset of it behind the write-combining scatter's own LDS
 std::size_t partition_hot_lds_bytes();
 

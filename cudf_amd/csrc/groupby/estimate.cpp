@@ -14,7 +14,7 @@ namespace cudf::groupby::detail {
 aggregate_call::aggregate_call(table_view const& keys, null_policy policy, std::span<aggregation_request const> requests, hipStream_t stream)
   : env{planner_env::load()},
     trace{env.trace},
-    hp{build_plan(keys, policy, requests, env)},
+    hp{build_plan(keys, policy, requests)},
     p{hp.dev},
     n{keys.num_rows()},
     s{stream},
@@ -28,7 +28,7 @@ aggregate_call::aggregate_call(table_view const& keys, null_policy policy, std::
   int const slot_bytes     = aggregate_slot_bytes(p);  // key units + accumulators (COUNTs take 4 bytes) + state word
   // a multiple of 4: the table is probed in aligned buckets of four slots (one ds_read_b128 of state words)
   ag.cap        = static_cast<int32_t>(std::min<int64_t>(lds_budget / slot_bytes, 16384)) & ~3;
-  ag.block      = static_cast<int32_t>(env.agg_block);
+  ag.block      = 1024;
   ag.fill_limit = static_cast<int32_t>(ag.cap * 0.6);
   CUDF_EXPECTS(ag.cap >= 64, "Aggregation state per group too large for an LDS table.");
   d_overflow = sc.alloc<int32_t>(1);
@@ -42,11 +42,10 @@ aggregate_call::aggregate_call(table_view const& keys, null_policy policy, std::
   // Composite dense keys: 1-4 integer key columns of any width (rows with a NULL key are dropped: no nullable key under
   // null_policy::INCLUDE), exactly one value column, no ARGMIN / ARGMAX
   dense_composite = !dense_candidate && p.nkeycols <= DENSE_MAX_KEYS && hp.value_cols.size() == 1 && p.narg == 0 &&
-                    hp.keynulls_unit < 0 && n >= env.one_table_min_rows && env.dense && env.dense_composite;
+                    hp.keynulls_unit < 0 && n >= env.one_table_min_rows && env.dense;
   for (int c = 0; c < p.nkeycols && dense_composite; ++c)
     dense_composite = p.cols[c].cls == cudf::detail::CLS_SINT || p.cols[c].cls == cudf::detail::CLS_UINT;
-  allow_dense      = dense_candidate || dense_composite;
-  allow_optimistic = env.optimistic;
+  allow_dense = dense_candidate || dense_composite;
 }
 
 // ---- the sample pass
@@ -57,14 +56,14 @@ void aggregate_call::estimate()
   // Small inputs skip the estimate (three memsets, three kernels and a stream synchronisation: about a third of a 10K-row call):
   // they are planned for one table per 16K-row chunk, and a table that overflows sends the call through escalate() - which
   // counts the keys over all rows - like any other misjudged cardinality.
-  bool const skip_estimate = n < env.estimate_min_rows;
+  bool const skip_estimate = n < (int64_t{1} << 16);
   if (skip_estimate && n > ag.fill_limit) est_groups = static_cast<double>(ag.fill_limit) / 1.3 - 1.0;
   if (n > ag.fill_limit && !skip_estimate) {
     // 1M sampled rows for big inputs; small inputs sample 1/16 of their rows (at least 64K): the estimate only picks the
     // strategy, and a 1M-row sample costs more than the aggregation of a 1M-row input
     // (round 4 tried n / 64: the 10M-row call 363 -> 340 us, but with 94K sampled rows of 6M a column with 30 % of its rows on 12 keys shows
-    // too few of its cold keys, looks sparse and leaves the dense path - CUDF_AMD_GB_SAMPLE_DIV stays 16)
-    int64_t const sample = std::min<int64_t>(n, std::clamp<int64_t>(n / std::max<int64_t>(env.sample_div, 1), int64_t{1} << 16, int64_t{1} << 20));
+    // too few of its cold keys, looks sparse and leaves the dense path - the divisor stays 16)
+    int64_t const sample = std::min<int64_t>(n, std::clamp<int64_t>(n / 16, int64_t{1} << 16, int64_t{1} << 20));
     // (linear counting wants the bitmap at a sixteenth of its load: 2^24 bits for the 1M-row sample of a big input, 2^20 for the
     // 64K-row sample of a 1M-row input - whose memset and population count were a 2 MB pass each for nothing)
     int bits_log2 = 16;
@@ -72,8 +71,7 @@ void aggregate_call::estimate()
     uint32_t* bitmap     = sc.alloc<uint32_t>((size_t{1} << bits_log2) / 32);
     uint32_t* d_set      = sc.alloc<uint32_t>(1);
     plan_dev* d_plan = sc.alloc<plan_dev>(1);
-    bool const hot_eligible = p.simple && RU == 2 && p.KU == 1 && hot_plan_ok(p) && n >= env.big_min_rows &&
-                              env.hot;
+    bool const hot_eligible = p.simple && RU == 2 && p.KU == 1 && hot_plan_ok(p) && n >= env.big_min_rows;
     uint32_t* hot_buckets = hot_eligible ? sc.alloc<uint32_t>(HOT_BUCKETS) : nullptr;
     // (one plain integer key column: the same pass takes the minimum and maximum of the sampled keys for the dense-key test)
     uint64_t* d_range = dense_candidate ? sc.alloc<uint64_t>(2) : nullptr;
@@ -285,8 +283,8 @@ aggregate_call::attempt_plan aggregate_call::plan_attempt() const
   // Planned table load. Bucketed probing resolves a row in two LDS round trips up to ~0.4; a lighter table means
   // more partitions. 16-byte records (write-combining scatter): halving the fan-out saves more in the scatter
   // (C2: 8.3 -> 7.1 ms) than the fuller tables cost the aggregate (3.1 -> 3.7 ms), so plan for 0.45/safety = 0.35.
-  bool const wc_eligible = (RU == 2 || RU == 3) && p.KU == 1 && env.wc;
-  double const plan_fill = std::max(1.0, ag.cap * 0.01 * static_cast<double>(env.plan_load_pct >= 0 ? env.plan_load_pct : (wc_eligible ? 45 : 25)));
+  bool const wc_eligible = (RU == 2 || RU == 3) && p.KU == 1;
+  double const plan_fill = std::max(1.0, ag.cap * 0.01 * (wc_eligible ? 45 : 25));
   // (groups <= rows, and the safety factor rides on top of that bound: more than `safety` x n / plan_fill tables are never needed
   // for the tables' MEAN load, but without it an all-distinct key column was planned at the full load with no slack)
   ap.need = std::min(est_groups, static_cast<double>(n)) * (est_groups >= static_cast<double>(n) ? safety : std::min(safety, static_cast<double>(n) / est_groups)) / plan_fill;
@@ -304,7 +302,7 @@ outcome aggregate_call::run_attempt(int attempt)
   attempt_plan ap = plan_attempt();
   outcome o = try_dense_one_table();                       // T: the key range fits ONE direct-address table
   if (o != outcome::skip) return o;
-  if (ap.fits_one_table && env.forced_p == 0) {
+  if (ap.fits_one_table) {
     o = run_single_pass(ap);                               // S: the groups fit one hash table
   } else {
     final_cap = 0;

@@ -30,28 +30,7 @@ __global__ void __launch_bounds__(1024) k_partition_hist(part_args const* __rest
       row[k]  = base + k * B + threadIdx.x;
       keep[k] = row[k] < sr.end;
     }
-    if (SIMPLE && from_cols && p.simple_vec16 && ((sr.begin & 1) == 0)) {
-      // two rows per 16-byte load (rows 2m, 2m+1); which lane counts which row does not matter for a histogram
-#pragma unroll
-      for (int m = 0; m < R / 2; ++m) {
-        int64_t const r = base + (static_cast<int64_t>(m) * B + threadIdx.x) * 2;
-        keep[2 * m]     = r < sr.end;
-        keep[2 * m + 1] = r + 1 < sr.end;
-#pragma unroll
-        for (int u = 0; u < MAX_KU; ++u) {
-          key[2 * m][u] = key[2 * m + 1][u] = 0;
-          if (u < p.KU) {
-            if (keep[2 * m + 1]) {
-              u64x2 const v     = gload(reinterpret_cast<u64x2 const*>(p.simple_base[u] + r));
-              key[2 * m][u]     = v.x;
-              key[2 * m + 1][u] = v.y;
-            } else if (keep[2 * m]) {
-              key[2 * m][u] = gload(p.simple_base[u] + r);
-            }
-          }
-        }
-      }
-    } else if (from_cols && !SIMPLE) {
+    if (from_cols && !SIMPLE) {
       uint32_t vv[R];
       batch_units<R, MAX_KU>(p, p.KU, row, keep, key, vv);
     } else {
@@ -126,16 +105,6 @@ __global__ void __launch_bounds__(1024) k_partition_scan(part_args const* __rest
 }
 
 // ------------------------------------------------------------------ K_scatter
-#ifdef SCATTER_NT_LOAD
-#define SCATTER_LOAD gload_stream
-#else
-#define SCATTER_LOAD gload
-#endif
-#ifdef SCATTER_NT_STORE
-#define SCATTER_STORE gstore_stream
-#else
-#define SCATTER_STORE gstore
-#endif
 // One workgroup per (segment, slice). Per tile of T = blockDim * RPT rows: rank rows inside their partition
 // with an LDS histogram, exclusive-scan the histogram, stage the records in LDS in partition order and write
 // them out so that consecutive lanes write consecutive records of one partition (runs of T/P records).
@@ -206,35 +175,9 @@ __global__ void __launch_bounds__(1024) k_partition_scatter(part_args const* __r
 
   uint64_t rec[RPT][UT];
   bool keep[RPT];
-  // loads one tile into registers (all loads issued back to back)
-  bool const vec16 = SIMPLE && (RPT % 2 == 0) && p.simple_vec16 && ((sr.begin & 1) == 0);
+  // loads one tile into registers (all loads issued back to back; one row per 8-byte load - pairs of rows per 16-byte load
+  // measured slower in both the histogram, 1.85 against 1.6 ms, and this kernel, 25.5M against 22.2M cycles per workgroup)
   auto load_tile = [&](int64_t tile) {
-    if constexpr (SIMPLE && (RPT % 2 == 0)) {
-      if (vec16) {
-        // 8-byte-per-lane loads run at 0.54-0.70x the 16-byte rate (the load issue was 51 % of the tile time):
-        // each lane takes rows (2m, 2m+1) of every column with one global_load_dwordx4
-#pragma unroll
-        for (int m = 0; m < RPT / 2; ++m) {
-          int64_t const r = tile + (static_cast<int64_t>(m) * B + threadIdx.x) * 2;
-          keep[2 * m]     = r < sr.end;
-          keep[2 * m + 1] = r + 1 < sr.end;
-          if (keep[2 * m + 1]) {
-#pragma unroll
-            for (int u = 0; u < UT; ++u) {
-              if (u < U) {
-                u64x2 const v     = gload(reinterpret_cast<u64x2 const*>(sbase[u] + r));
-                rec[2 * m][u]     = v.x;
-                rec[2 * m + 1][u] = v.y;
-              }
-            }
-          } else if (keep[2 * m]) {
-#pragma unroll
-            for (int u = 0; u < UT; ++u) rec[2 * m][u] = (u < U) ? gload(sbase[u] + r) : 0;
-          }
-        }
-        return;
-      }
-    }
     if (!SIMPLE && from_cols) {
       int64_t row[RPT];
       uint32_t vv[RPT];
@@ -252,12 +195,11 @@ __global__ void __launch_bounds__(1024) k_partition_scatter(part_args const* __r
       keep[k]         = r < sr.end;
       if (keep[k]) {
         if constexpr (SIMPLE) {
-          if (vec16) continue;  // loaded two rows at a time below
 #pragma unroll
-          for (int u = 0; u < UT; ++u) rec[k][u] = (u < U) ? SCATTER_LOAD(sbase[u] + r) : 0;
+          for (int u = 0; u < UT; ++u) rec[k][u] = (u < U) ? gload(sbase[u] + r) : 0;
         } else if constexpr (EXACT && UT == 2) {
           int64_t const ri = from_regions ? rin.record_of(r) : r;
-          u64x2 const v = SCATTER_LOAD(reinterpret_cast<u64x2 const*>(in_records) + ri);
+          u64x2 const v = gload(reinterpret_cast<u64x2 const*>(in_records) + ri);
           rec[k][0]     = v.x;
           rec[k][1]     = v.y;
         } else {
@@ -266,16 +208,6 @@ __global__ void __launch_bounds__(1024) k_partition_scatter(part_args const* __r
           for (int u = 0; u < UT; ++u) rec[k][u] = (u < U) ? gload(in_records + ri * U + u) : 0;
         }
       }
-    }
-  };
-  unsigned long long ph[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-  bool const stamp = a.stamps != nullptr && threadIdx.x == 0;
-  unsigned long long t_prev = stamp ? __builtin_amdgcn_s_memtime() : 0;
-  auto mark = [&](int i) {
-    if (stamp) {
-      unsigned long long const t = __builtin_amdgcn_s_memtime();
-      ph[i] += t - t_prev;
-      t_prev = t;
     }
   };
   if (sr.begin < sr.end) load_tile(sr.begin);
@@ -293,9 +225,7 @@ __global__ void __launch_bounds__(1024) k_partition_scatter(part_args const* __r
         rank[k] = atomicAdd(&hist[dig[k]], 1u);
       }
     }
-    mark(0);
     lds_barrier();
-    mark(1);
     // phase 2: hist -> exclusive local offsets (in place); delta = global cursor - local offset
     uint32_t hv[MAXE], local = 0;
 #pragma unroll
@@ -318,7 +248,6 @@ __global__ void __launch_bounds__(1024) k_partition_scatter(part_args const* __r
       }
     }
     lds_barrier();
-    mark(2);
     if (s_abort) {
       if (threadIdx.x == 0) *a.overflow = 1;
       return;
@@ -340,11 +269,8 @@ __global__ void __launch_bounds__(1024) k_partition_scatter(part_args const* __r
     }
     // the records are staged: the registers are free, so the NEXT tile's loads go out now and fly under the
     // write-out phase (one workgroup per CU: nothing else would hide their latency)
-    mark(3);
     if (tile + T < sr.end) load_tile(tile + T);
-    mark(4);
     lds_barrier();
-    mark(5);
 #pragma unroll
     for (int k = 0; k < MAXE; ++k) {
       int const d = threadIdx.x * MAXE + k;
@@ -354,20 +280,14 @@ __global__ void __launch_bounds__(1024) k_partition_scatter(part_args const* __r
     for (uint32_t j = threadIdx.x; j < tile_count; j += B) {
       int64_t const dst = delta[pid[j]] + static_cast<int64_t>(j);
       if constexpr (EXACT && UT == 2) {
-        SCATTER_STORE(reinterpret_cast<u64x2*>(out_records) + dst, reinterpret_cast<u64x2 const*>(stage)[j]);
+        gstore(reinterpret_cast<u64x2*>(out_records) + dst, reinterpret_cast<u64x2 const*>(stage)[j]);
       } else {
 #pragma unroll
         for (int u = 0; u < UT; ++u)
           if (u < U) gstore(out_records + dst * U + u, stage[static_cast<size_t>(j) * U + u]);
       }
     }
-    mark(6);
     lds_barrier();
-    mark(7);
-  }
-  if (stamp) {
-#pragma unroll
-    for (int i = 0; i < 8; ++i) a.stamps[static_cast<int64_t>(blockIdx.x) * 8 + i] = ph[i];
   }
   if (optimistic) {
 #pragma unroll
@@ -390,9 +310,8 @@ constexpr int WC_SRC_RECORDS = 2;  // records: one contiguous range, or a stride
 constexpr int WC_SRC_DENSE_COLS = 3;  // composite dense keys: 1-4 integer key columns + one value column -> {index | validity, value}
 // HOT: heavy-hitter keys (part_args::hot_*) are aggregated in a small LDS table and never scattered.
 // DENSE: the partition digit comes from the dense key map (part_args::dense) instead of the key hash.
-// `chunk`: rows [begin, end) of the input columns (end == 0: all rows) - the chunked pipeline partitions one chunk per launch.
 template <int UT, int RPT, int G, int SRC, bool HOT = false, bool DENSE = false>
-__global__ void __launch_bounds__(1024) k_partition_scatter_wc(part_args const* __restrict__ ap, chunk_range chunk)
+__global__ void __launch_bounds__(1024) k_partition_scatter_wc(part_args const* __restrict__ ap)
 {
   extern __shared__ __attribute__((aligned(16))) unsigned char lds_raw[];
   part_args const& a = *ap;
@@ -424,6 +343,10 @@ __global__ void __launch_bounds__(1024) k_partition_scatter_wc(part_args const* 
   }
   __shared__ int32_t s_pre[MAX_REGION_LIST + 1];
   constexpr bool SIMPLE = SRC == WC_SRC_SIMPLE;
+  // Tile-cyclic rows over the input columns (every source but records): workgroup w takes tiles w, w + slices, ... so that
+  // every workgroup sees the whole row range. With a contiguous chunk per workgroup, sorted or clustered keys put a chunk's
+  // rows into a few partitions and overflowed their regions.
+  constexpr bool CYCLIC = SRC != WC_SRC_RECORDS;
   region_input rin{};
   int const from_regions = SRC == WC_SRC_RECORDS ? a.from_regions : 0;
   slice_range sr;
@@ -434,13 +357,9 @@ __global__ void __launch_bounds__(1024) k_partition_scatter_wc(part_args const* 
     sr.end       = rin.total();
   } else {
     sr = slice_of(a, blockIdx.x);
-    // Tile-cyclic rows (optimistic partition of the input columns): workgroup w takes tiles w, w + slices, ... so that
-    // every workgroup sees the whole row range. With a contiguous chunk per workgroup, sorted or clustered keys put a
-    // chunk's rows into a few partitions and overflowed their regions.
-    if (a.cyclic_tiles) {
-      int64_t const cb = chunk.end > 0 ? chunk.begin : 0, ce = chunk.end > 0 ? chunk.end : a.nrows;
-      sr.begin = min(ce, cb + static_cast<int64_t>(blockIdx.x) * (RPT * B));
-      sr.end   = ce;
+    if constexpr (CYCLIC) {
+      sr.begin = min(a.nrows, static_cast<int64_t>(blockIdx.x) * (RPT * B));
+      sr.end   = a.nrows;
     }
   }
   uint64_t const* in_records = a.in_records;
@@ -553,7 +472,7 @@ __global__ void __launch_bounds__(1024) k_partition_scatter_wc(part_args const* 
   g.item         = from_regions ? blockIdx.x % a.geom.slices : blockIdx.x;
   g.begin        = sr.begin;
   g.end          = sr.end;
-  g.step         = (!from_regions && a.cyclic_tiles) ? static_cast<int64_t>(a.geom.slices) * (RPT * B) : 0;
+  g.step         = CYCLIC ? static_cast<int64_t>(a.geom.slices) * (RPT * B) : 0;
   g.region_cap   = a.region_cap;
   g.region_count = a.region_count + region0;
   g.overflow     = a.overflow;
@@ -627,53 +546,51 @@ static void launch_scatter_t(part_args const& a, part_args const* d_args, hipStr
 
 // Tile rows per thread and granule of the write-combining kernel for a record width; 0 = no instantiation.
 int wc_rpt(int U) { return U == 2 ? 5 : U == 3 ? 4 : U == 4 ? 3 : 0; }
-bool partition_wc_fits(int U, int P, int G, int block)
+bool partition_wc_fits(int U, int P, int G)
 {
   int const rpt = wc_rpt(U);
   // 24-byte records: 192-byte granules (G = 8), or 96-byte ones (G = 4: whole 32-byte sectors) where the carry area of
   // G = 8 does not fit; 32-byte records: 128-byte granules
   if (rpt == 0 || (G != 4 && G != 8) || (U == 4 && G != 4)) return false;
   // static LDS of the kernel (region prefix list, abort flag) is ~1.1 KB
-  return P <= 2 * block && cudf::detail::wc_scatter_lds_bytes(static_cast<std::size_t>(block) * rpt, P, G, U) + 1200 <= (block == 1024 ? 160 : 80) * 1024;
+  return P <= 2 * 1024 && cudf::detail::wc_scatter_lds_bytes(std::size_t{1024} * rpt, P, G, U) + 1200 <= 160 * 1024;
 }
 
 std::size_t partition_hot_lds_bytes() { return static_cast<std::size_t>(HOT_SLOTS) * (8 + 8 + 4); }
 
 template <int UT, int RPT, int G, int SRC, bool HOT = false, bool DENSE = false>
-static void launch_scatter_wc_src(part_args const& a, part_args const* d_args, hipStream_t stream, chunk_range chunk)
+static void launch_scatter_wc_src(part_args const& a, part_args const* d_args, hipStream_t stream)
 {
   part_geom g  = a.geom;
   g.tile_rows  = g.block * RPT;
   auto const lds = cudf::detail::wc_scatter_lds_bytes(g.tile_rows, g.P, G, UT) + (HOT ? partition_hot_lds_bytes() : 0);
   CUDF_EXPECTS(lds + 1200 <= 160 * 1024, "write-combining partition kernel: LDS budget exceeded");
-  CUDF_EXPECTS(!HOT || g.block == 1024, "heavy hitters: 1024-thread scatter workgroups");
   static std::once_flag attr_once;  // (the API is re-entrant across objects: two threads may launch this kernel first)
   std::call_once(attr_once, [] { allow_full_lds(reinterpret_cast<void const*>(&k_partition_scatter_wc<UT, RPT, G, SRC, HOT, DENSE>)); });
   cudf::detail::prof::scope prof_{a.from_columns ? "partition_scatter" : "partition_scatter_level2", stream};
-  hipLaunchKernelGGL((k_partition_scatter_wc<UT, RPT, G, SRC, HOT, DENSE>), dim3(g.nseg * g.slices), dim3(g.block), lds, stream, d_args, chunk);
+  hipLaunchKernelGGL((k_partition_scatter_wc<UT, RPT, G, SRC, HOT, DENSE>), dim3(g.nseg * g.slices), dim3(g.block), lds, stream, d_args);
   CUDF_HIP_TRY(hipGetLastError());
 }
 
 template <int UT, int RPT, int G>
-static void launch_scatter_wc_t(part_args const& a, part_args const* d_args, hipStream_t stream, chunk_range chunk)
+static void launch_scatter_wc_t(part_args const& a, part_args const* d_args, hipStream_t stream)
 {
   if constexpr (UT == 2) {
-    if (!a.from_columns && a.use_dense) return launch_scatter_wc_src<UT, RPT, G, WC_SRC_RECORDS, false, true>(a, d_args, stream, chunk);
+    if (!a.from_columns && a.use_dense) return launch_scatter_wc_src<UT, RPT, G, WC_SRC_RECORDS, false, true>(a, d_args, stream);
     // (4 rows per thread: with 5 the column loader spilled 21 registers to scratch)
-    if (a.from_columns && a.use_dense && a.dense.nkeys > 0) return launch_scatter_wc_src<UT, 4, G, WC_SRC_DENSE_COLS, false, true>(a, d_args, stream, chunk);
+    if (a.from_columns && a.use_dense && a.dense.nkeys > 0) return launch_scatter_wc_src<UT, 4, G, WC_SRC_DENSE_COLS, false, true>(a, d_args, stream);
   }
-  if (!a.from_columns) return launch_scatter_wc_src<UT, RPT, G, WC_SRC_RECORDS>(a, d_args, stream, chunk);
+  if (!a.from_columns) return launch_scatter_wc_src<UT, RPT, G, WC_SRC_RECORDS>(a, d_args, stream);
   if constexpr (UT == 2) {
-    if (a.plan.simple && a.use_dense) return launch_scatter_wc_src<UT, RPT, G, WC_SRC_SIMPLE, false, true>(a, d_args, stream, chunk);
-    if (a.plan.simple && a.hot_n > 0) return launch_scatter_wc_src<UT, RPT, G, WC_SRC_SIMPLE, true>(a, d_args, stream, chunk);
+    if (a.plan.simple && a.use_dense) return launch_scatter_wc_src<UT, RPT, G, WC_SRC_SIMPLE, false, true>(a, d_args, stream);
+    if (a.plan.simple && a.hot_n > 0) return launch_scatter_wc_src<UT, RPT, G, WC_SRC_SIMPLE, true>(a, d_args, stream);
   }
-  if (a.plan.simple) return launch_scatter_wc_src<UT, RPT, G, WC_SRC_SIMPLE>(a, d_args, stream, chunk);
-  return launch_scatter_wc_src<UT, RPT, G, WC_SRC_COLUMNS>(a, d_args, stream, chunk);
+  if (a.plan.simple) return launch_scatter_wc_src<UT, RPT, G, WC_SRC_SIMPLE>(a, d_args, stream);
+  return launch_scatter_wc_src<UT, RPT, G, WC_SRC_COLUMNS>(a, d_args, stream);
 }
 
-void launch_partition_scatter(part_args const& a, part_args const* d_args, hipStream_t stream, chunk_range chunk)
+void launch_partition_scatter(part_args const& a, part_args const* d_args, hipStream_t stream)
 {
-  CUDF_EXPECTS(chunk.end == 0 || (a.wc_granule != 0 && a.from_columns && a.cyclic_tiles), "chunked scatter: write-combining kernel over the input columns only");
   CUDF_EXPECTS(!a.use_dense || (a.wc_granule != 0 && (a.dense.nkeys > 0 || !a.from_columns || (a.plan.simple && a.plan.KU + a.plan.NPAY == 2))),
                "dense keys: 16-byte records only");
   CUDF_EXPECTS(a.geom.P <= 2 * a.geom.block, "partition fan-out exceeds 2x the block size");
@@ -681,22 +598,17 @@ void launch_partition_scatter(part_args const& a, part_args const* d_args, hipSt
   int const U       = (a.use_dense && (a.dense.nkeys > 0 || !a.from_columns)) ? 2 : a.plan.KU + a.plan.NPAY;
   bool const simple = a.plan.simple && a.from_columns;
   if (a.wc_granule != 0) {
-    CUDF_EXPECTS(a.optimistic && (a.geom.block == 1024 || a.geom.block == 512) && partition_wc_fits(U, a.geom.P, a.wc_granule, a.geom.block),
+    CUDF_EXPECTS(a.optimistic && a.geom.block == 1024 && partition_wc_fits(U, a.geom.P, a.wc_granule),
                  "write-combining scatter: optimistic regions, records of 2-4 units, carry area within the LDS");
-    if (U == 2 && a.wc_granule == 4) launch_scatter_wc_t<2, 5, 4>(a, d_args, stream, chunk);
-    else if (U == 2) launch_scatter_wc_t<2, 5, 8>(a, d_args, stream, chunk);
-    else if (U == 3 && a.wc_granule == 4) launch_scatter_wc_t<3, 4, 4>(a, d_args, stream, chunk);
-    else if (U == 3) launch_scatter_wc_t<3, 4, 8>(a, d_args, stream, chunk);
-    else launch_scatter_wc_t<4, 3, 4>(a, d_args, stream, chunk);
+    if (U == 2 && a.wc_granule == 4) launch_scatter_wc_t<2, 5, 4>(a, d_args, stream);
+    else if (U == 2) launch_scatter_wc_t<2, 5, 8>(a, d_args, stream);
+    else if (U == 3 && a.wc_granule == 4) launch_scatter_wc_t<3, 4, 4>(a, d_args, stream);
+    else if (U == 3) launch_scatter_wc_t<3, 4, 8>(a, d_args, stream);
+    else launch_scatter_wc_t<4, 3, 4>(a, d_args, stream);
     return;
   }
   switch (next_ut(U)) {
-    case 2:
-      if (a.geom.tile_rows == 4 * a.geom.block)  // half-size tile: 64 KiB of LDS, two workgroups per CU
-        simple ? launch_scatter_t<2, 4, true, true>(a, d_args, stream) : launch_scatter_t<2, 4, false, true>(a, d_args, stream);
-      else
-        simple ? launch_scatter_t<2, 8, true, true>(a, d_args, stream) : launch_scatter_t<2, 8, false, true>(a, d_args, stream);
-      break;
+    case 2: simple ? launch_scatter_t<2, 8, true, true>(a, d_args, stream) : launch_scatter_t<2, 8, false, true>(a, d_args, stream); break;
     case 3: simple ? launch_scatter_t<3, 4, true, true>(a, d_args, stream) : launch_scatter_t<3, 4, false, true>(a, d_args, stream); break;
     case 4: simple ? launch_scatter_t<4, 4, true, true>(a, d_args, stream) : launch_scatter_t<4, 4, false, true>(a, d_args, stream); break;
     case 6: launch_scatter_t<6, 2, false, false>(a, d_args, stream); break;

@@ -16,7 +16,7 @@ namespace cudf::groupby::detail {
 // (no hash, no probe, no key compare, no partition pass) and k_dense_merge_dump_wide folds the images.
 outcome aggregate_call::try_dense_one_table()
 {
-    if (env.forced_p == 0 && allow_dense && env.dense_one_table) {
+    if (allow_dense && env.dense_one_table) {
       dense_map dm{};
       bool ok = dense_map_from_sample(dm, true);
       int bits = 6;
@@ -85,7 +85,7 @@ outcome aggregate_call::try_dense_ring()
   // (heavy hitters in the sample: only the single-level ring scatter of one plain key takes them out of the partition)
   bool const ring_env = env.dense_ring;
   // (below big_min_rows only the one-table path T is tried: the partition passes are for big inputs)
-  if (!(allow_dense && n >= env.big_min_rows && env.forced_p == 0 && (hot_keys.empty() || (dense_candidate && ring_env)) && !env.exact)) return outcome::skip;
+  if (!(allow_dense && n >= env.big_min_rows && (hot_keys.empty() || (dense_candidate && ring_env)))) return outcome::skip;
   if (dense_candidate && p.NPAY > 1) return ring_env ? try_dense_ring_multi() : outcome::skip;  // one value stream per column
       dense_map dm{};
       bool dense_ok = dense_map_from_sample(dm);
@@ -133,7 +133,6 @@ outcome aggregate_call::try_dense_ring()
             dense_ring_args ra{};
             ra.plan         = p;
             ra.map          = dm;
-            ra.static_shapes = static_cast<int32_t>(env.static_shapes);
             ra.from_columns = 1;
             ra.nrows        = n;
             ra.P            = static_cast<int32_t>(PD);
@@ -225,7 +224,7 @@ outcome aggregate_call::try_dense_ring()
             store_args(da, d_da, s);
             launch_dense_ring_scatter(ra, d_ra, s);
             if (two_level) launch_dense_ring_scatter(rb, d_rb, s);
-            launch_aggregate_dense(da, d_da, true, true, s);
+            launch_aggregate_dense(da, d_da, s);
             if (nsplit > 1) launch_dense_merge_dump(da, d_da, nsplit, s);
             final_cap          = slots / nsplit;
             if (ring_hot) {  // the workgroups' heavy-hitter partials -> one more item behind the tables' (hash-table merge kernel)
@@ -380,7 +379,7 @@ outcome aggregate_call::try_dense_ring_multi()
     da.block        = 1024;
     dense_agg_args* d_da = sc.alloc<dense_agg_args>(1);
     store_args(da, d_da, s);
-    launch_aggregate_dense(da, d_da, true, true, s);
+    launch_aggregate_dense(da, d_da, s);
     ma.tables[c]      = da.tables;
     ma.image_bytes[c] = da.image_bytes;
   }
@@ -412,11 +411,12 @@ outcome aggregate_call::try_dense_ring_multi()
 }
 
 // ---- write-combining scatter with 16-byte records (CUDF_AMD_GB_DENSE_RING=0, or a geometry the rings do not take). (Rounds 2-3 could
-// also run it chunk by chunk through the Infinity Cache; measured slower - profiles/r2_mall_pipeline.txt - and removed in round 4.)
+// also run it chunk by chunk through the Infinity Cache, or with two 512-thread scatter workgroups per CU and 64-byte granules; both
+// measured slower - profiles/r2_mall_pipeline.txt - and were removed.)
 outcome aggregate_call::try_dense_wc()
 {
   bool const ring_env = env.dense_ring;
-  if (!(allow_dense && n >= env.big_min_rows && env.forced_p == 0 && (hot_keys.empty() || (dense_candidate && ring_env)) && !env.exact)) return outcome::skip;
+  if (!(allow_dense && n >= env.big_min_rows && (hot_keys.empty() || (dense_candidate && ring_env)))) return outcome::skip;
   if (dense_candidate && p.NPAY > 1) return outcome::skip;  // (16-byte records carry one value)
       dense_map dm{};
       bool dense_ok = dense_map_from_sample(dm);
@@ -438,11 +438,9 @@ outcome aggregate_call::try_dense_wc()
         dense_ok = dense_ok && dm.range <= (uint64_t{1} << bits) && bits <= 30 && bits - log2P >= 6 && log2P <= 20 && image <= 150 * 1024 &&
                    static_cast<double>(dm.range) <= 8.0 * std::max(est_groups, 4096.0);
         int64_t const PD = int64_t{1} << log2P1, P2D = int64_t{1} << log2P2;
-        // scatter workgroups: one of 1024 threads per CU (128-byte granules up to 512 partitions), or - CUDF_AMD_GB_SCATTER_BLOCK=512 -
-        // two of 512 threads per CU with 64-byte granules (measured slower: profiles/r2_mall_pipeline.txt)
-        int const SB     = env.scatter_block == 512 ? 512 : 1024;
-        int const GD     = static_cast<int>((env.wc_g >= 0 ? env.wc_g : ((PD > 512 || SB == 512) ? 4 : 8)));
-        if (dense_ok && partition_wc_fits(2, static_cast<int>(PD), GD, SB) && (!two_level || partition_wc_fits(2, static_cast<int>(P2D), P2D > 512 ? 4 : 8))) {
+        // scatter workgroups: one of 1024 threads per CU, 128-byte granules up to 512 partitions
+        int const GD     = PD > 512 ? 4 : 8;
+        if (dense_ok && partition_wc_fits(2, static_cast<int>(PD), GD) && (!two_level || partition_wc_fits(2, static_cast<int>(P2D), P2D > 512 ? 4 : 8))) {
           path  = hash_path::DENSE_DIRECT;
           dm.mult     = 0x9E3779B1u;  // odd: index -> (index * mult) mod 2^bits is a bijection
           uint32_t inv = dm.mult;     // Newton: inv = mult^-1 mod 2^32
@@ -451,7 +449,7 @@ outcome aggregate_call::try_dense_wc()
           dm.bits     = bits;
           dm.log2P    = log2P;
           int const DPU = (dm.nkeys > 0 ? p.KU : 1) + p.NACC;  // units of a dumped partial record
-          int64_t const S        = 256 * (1024 / SB), tile_rows = 5 * SB;
+          int64_t const S        = 256;
           double const cell_mean = static_cast<double>(n) / static_cast<double>(S * PD);
           double const keys_per_p = std::max(1.0, 0.5 * est_groups / static_cast<double>(PD));
           double const rel_sigma  = std::sqrt(1.0 / keys_per_p + 1.0 / std::max(1.0, cell_mean));
@@ -462,8 +460,8 @@ outcome aggregate_call::try_dense_wc()
           pa.geom.slices   = static_cast<int32_t>(S);
           pa.geom.P        = static_cast<int32_t>(PD);
           pa.geom.shift    = bits - log2P1;  // level 1: the top log2P1 bits of the scrambled index
-          pa.geom.block    = SB;
-          pa.geom.tile_rows = static_cast<int32_t>(tile_rows);
+          pa.geom.block    = 1024;
+          pa.geom.tile_rows = 5 * 1024;
           pa.from_columns  = 1;
           pa.nrows         = n;
           pa.optimistic    = 1;
@@ -472,7 +470,6 @@ outcome aggregate_call::try_dense_wc()
           pa.overflow      = d_overflow;
           pa.out_records   = sc.alloc<uint64_t>(static_cast<size_t>(S * PD) * static_cast<size_t>(capR) * 2);
           pa.wc_granule    = GD;
-          pa.cyclic_tiles  = 1;
           pa.use_dense     = 1;
           pa.dense         = dm;
           part_args* d_pa  = sc.alloc<part_args>(1);
@@ -540,7 +537,7 @@ outcome aggregate_call::try_dense_wc()
           store_args(da, d_da, s);
           launch_partition_scatter(pa, d_pa, s);
           if (two_level) launch_partition_scatter(pb, d_pb, s);
-          launch_aggregate_dense(da, d_da, true, true, s);
+          launch_aggregate_dense(da, d_da, s);
           final_cap          = slots;
           int32_t const h_ov = overflow_and_counts();
           if (env.debug)

@@ -114,7 +114,7 @@ outcome aggregate_call::run_single_pass(attempt_plan& ap)
   agg_args& aa = ap.aa;
       // ---------------- path S: every workgroup aggregates a row chunk in LDS, then partials are merged
       path          = hash_path::LDS_SINGLE_PASS;
-      int64_t const items = std::clamp<int64_t>(n / 16384, 1, env.s_items);
+      int64_t const items = std::clamp<int64_t>(n / 16384, 1, 1024);
       nitems              = static_cast<int32_t>(items);
       partial             = sc.alloc<uint64_t>(static_cast<size_t>(nitems) * ag.cap * PU);
       d_count             = sc.alloc<int32_t>(nitems);
@@ -161,7 +161,7 @@ outcome aggregate_call::run_single_pass(attempt_plan& ap)
 outcome aggregate_call::try_preaggregate(attempt_plan& ap)
 {
   agg_args& aa = ap.aa;
-      if (adjacent_equal >= 0.01 * static_cast<double>(env.preagg_min_pct) && !pre_failed && env.forced_p == 0 && p.narg == 0) {
+      if (adjacent_equal >= 0.90 && !pre_failed && p.narg == 0) {
         double const run_starts = std::max(1.0 - adjacent_equal, 1e-6);  // distinct keys of a chunk <= its run starts
         // (and at least ~2048 chunks: long runs would otherwise leave most CUs without a chunk - 200M sorted rows on 100K groups
         // ran on 48 workgroups, 5.1 ms)
@@ -261,8 +261,7 @@ outcome aggregate_call::try_preaggregate(attempt_plan& ap)
 // 16-byte records at P = 1024 (a 128-byte carry area would not leave room for a tile), else 128-256 bytes
 int32_t aggregate_call::wc_granule_for(int64_t P) const
 {
-  if (!env.wc) return 0;
-  int const G = RU == 2 ? static_cast<int>(env.wc_g >= 0 ? env.wc_g : (P > 512 ? 4 : 8)) : (RU == 4 ? 4 : 8);
+  int const G = RU == 2 ? (P > 512 ? 4 : 8) : (RU == 4 ? 4 : 8);
   if (partition_wc_fits(RU, static_cast<int>(P), G)) return G;
   return (RU == 3 && partition_wc_fits(RU, static_cast<int>(P), 4)) ? 4 : 0;  // 24-byte records: 96-byte granules
 }
@@ -278,9 +277,9 @@ outcome aggregate_call::run_partitioned(attempt_plan& ap)
         return v;
       };
       int64_t const maxP1 = 1024;  // LDS: 8192-row stage + P * 12 B + pid must fit 160 KiB
-      int64_t P1 = env.forced_p ? env.forced_p : std::clamp<int64_t>(pow2_at_least(ap.need), 256, maxP1);
+      int64_t P1 = std::clamp<int64_t>(pow2_at_least(ap.need), 256, maxP1);
       int64_t P2 = 1;
-      if (!env.forced_p && ap.need > static_cast<double>(maxP1)) {
+      if (ap.need > static_cast<double>(maxP1)) {
         int64_t const tot = pow2_at_least(ap.need);
         P1 = pow2_at_least(std::sqrt(static_cast<double>(tot)));
         P2 = tot / P1;
@@ -296,13 +295,13 @@ outcome aggregate_call::run_partitioned(attempt_plan& ap)
       pa.geom.nseg    = 1;
       // optimistic: one persistent workgroup per CU (longer regions for the aggregate); exact: 2 per CU (the
       // histogram pass wants the parallelism: 1.6 ms at 512 slices vs 2.7 ms at 256)
-      bool const will_try_optimistic = allow_optimistic && P2 == 1 && !env.exact && n >= (int64_t{1} << 22);
+      bool const will_try_optimistic = allow_optimistic && P2 == 1 && n >= (int64_t{1} << 22);
       // (small inputs: one slice per 16K rows - the single-workgroup scan walks slices x P counters)
-      pa.geom.slices  = static_cast<int32_t>((env.slices >= 0 ? env.slices : (will_try_optimistic ? 256 : std::clamp<int64_t>(n / 16384, 16, 512))));
+      pa.geom.slices  = static_cast<int32_t>(will_try_optimistic ? 256 : std::clamp<int64_t>(n / 16384, 16, 512));
       pa.geom.P       = static_cast<int32_t>(P1);
       pa.geom.shift   = 64 - log2P1;
       pa.geom.block   = 1024;
-      pa.geom.tile_rows = static_cast<int32_t>(env.rpt) * 1024;
+      pa.geom.tile_rows = 8 * 1024;
       pa.from_columns = 1;
       pa.nrows        = n;
       size_t const items1 = static_cast<size_t>(pa.geom.slices);
@@ -315,7 +314,7 @@ outcome aggregate_call::run_partitioned(attempt_plan& ap)
       // (half the estimated key count: an over-estimate would under-size the regions)
       double const keys_per_p  = std::max(1.0, 0.5 * est_groups / static_cast<double>(P1));
       double const rel_sigma   = std::sqrt(1.0 / keys_per_p + 1.0 / std::max(1.0, cell_mean));
-      bool const optimistic = allow_optimistic && P2 == 1 && !env.exact && n >= (int64_t{1} << 22) && 6.0 * rel_sigma <= 1.0;
+      bool const optimistic = allow_optimistic && P2 == 1 && n >= (int64_t{1} << 22) && 6.0 * rel_sigma <= 1.0;
       partition_plan const pp{P1, P2, log2P1, log2P2};
       if (optimistic) return try_optimistic_one_level(ap, pp, pa, d_pa);
       outcome const o2 = try_optimistic_two_level(ap, pp, pa, d_pa);
@@ -346,21 +345,9 @@ outcome aggregate_call::try_optimistic_one_level(attempt_plan& ap, partition_pla
         // 16-byte records: write-combining scatter (whole aligned granules only); 64-byte granules at P = 1024
         // (the carry area of 128-byte granules would not leave room for a tile), 128-byte granules at P <= 512
         pa.wc_granule = wc_granule_for(P1);
-        pa.cyclic_tiles = pa.wc_granule != 0 && env.cyclic;
         bool const hot = setup_hot(pa, P1);
-        if (env.stamps) pa.stamps = sc.alloc<unsigned long long>(items1 * 8);
         store_args(pa, d_pa, s);
         launch_partition_scatter(pa, d_pa, s);
-        if (pa.stamps != nullptr) {
-          std::vector<unsigned long long> h(items1 * 8);
-          CUDF_HIP_TRY(hipMemcpyAsync(h.data(), pa.stamps, h.size() * 8, hipMemcpyDeviceToHost, s));
-          CUDF_HIP_TRY(hipStreamSynchronize(s));
-          double tot[8] = {0};
-          for (size_t w = 0; w < items1; ++w) for (int i = 0; i < 8; ++i) tot[i] += static_cast<double>(h[w * 8 + i]);
-          double all = 0; for (double t : tot) all += t;
-          fprintf(stderr, "[cudf_amd] scatter phase shares (wave 0 of each WG, s_memtime): rank %.1f%% | barrier %.1f%% | scan %.1f%% | stage %.1f%% | prefetch-issue %.1f%% | barrier %.1f%% | write-out %.1f%% | barrier %.1f%%  (avg cycles/WG %.0f)\n",
-                  100 * tot[0] / all, 100 * tot[1] / all, 100 * tot[2] / all, 100 * tot[3] / all, 100 * tot[4] / all, 100 * tot[5] / all, 100 * tot[6] / all, 100 * tot[7] / all, all / items1);
-        }
         if (env.debug) { CUDF_HIP_TRY(hipStreamSynchronize(s)); fprintf(stderr, "[cudf_amd] optimistic scatter done capR=%ld P=%ld slices=%zu\n", (long)capR, (long)P1, items1); }
         nitems         = static_cast<int32_t>(P1);
         partial        = sc.alloc<uint64_t>(static_cast<size_t>(nitems + 1) * ag.cap * PU);
@@ -399,7 +386,7 @@ outcome aggregate_call::try_optimistic_two_level(attempt_plan& ap, partition_pla
   int const log2P1 = pp.log2P1, log2P2 = pp.log2P2;
   uint64_t* recA   = nullptr;
       bool const warm_tail = hot_keys.size() >= static_cast<std::size_t>(HOT_MAX_KEYS);
-      if (allow_optimistic && P2 > 1 && !env.exact && !warm_tail && n >= (int64_t{1} << 22) && env.optimistic2) {
+      if (allow_optimistic && P2 > 1 && !warm_tail && n >= (int64_t{1} << 22) && env.optimistic2) {
         int64_t const S1      = 256;
         int64_t const slices2 = std::max<int64_t>(1, 512 / P1);
         double const mean1    = static_cast<double>(n) / static_cast<double>(S1 * P1);
@@ -419,7 +406,6 @@ outcome aggregate_call::try_optimistic_two_level(attempt_plan& ap, partition_pla
           recA               = sc.alloc<uint64_t>(static_cast<size_t>(S1 * P1) * static_cast<size_t>(cap1) * RU);
           pa.out_records     = recA;
           pa.wc_granule      = wc_granule_for(P1);
-          pa.cyclic_tiles    = pa.wc_granule != 0 && env.cyclic;
           bool const hot     = setup_hot(pa, P1);  // (a key with percents of the rows would leave one table's workgroup alone with them)
           store_args(pa, d_pa, s);
           launch_partition_scatter(pa, d_pa, s);

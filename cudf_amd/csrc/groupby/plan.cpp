@@ -3,10 +3,10 @@
 // switches. Reference counterparts: cpp/src/groupby/hash/extract_single_pass_aggs.cpp:26-177 (flattening of the requests into
 // single-pass aggregations), groupby/common/utils.hpp:66-85 (the hashable set).
 #include "call.hpp"
+#include "../common/env.hpp"
 
 #include <algorithm>
 #include <cmath>
-#include <cstdlib>
 #include <cstring>
 
 namespace cudf::groupby::detail {
@@ -18,54 +18,26 @@ using cudf::detail::CLS_SINT;
 using cudf::detail::CLS_UINT;
 using cudf::detail::class_of;
 
-namespace {
-int64_t env_i64(char const* name, int64_t dflt)
-{
-  char const* e = std::getenv(name);
-  return (e != nullptr && *e != 0) ? std::strtoll(e, nullptr, 10) : dflt;
-}
-}  // namespace
-
 planner_env planner_env::load()
 {
+  using cudf::detail::env_i64;
   planner_env e{};
-  e.lds_kb            = env_i64("CUDF_AMD_GB_LDS_KB", 159);  // 160 KiB minus the kernels' static words
-  e.agg_block         = env_i64("CUDF_AMD_GB_AGG_BLOCK", 1024);
-  e.big_min_rows      = env_i64("CUDF_AMD_GB_BIG_MIN_ROWS", int64_t{1} << 22);
-  e.sample_div        = env_i64("CUDF_AMD_GB_SAMPLE_DIV", 16);
+  e.lds_kb             = env_i64("CUDF_AMD_GB_LDS_KB", 159);  // 160 KiB minus the kernels' static words
+  e.big_min_rows       = env_i64("CUDF_AMD_GB_BIG_MIN_ROWS", int64_t{1} << 22);
   // (the one-table path T needs no partition pass: it pays from far fewer rows - 1M rows on 1000 groups 260 -> ~150 us)
-  e.one_table_min_rows = std::min(e.big_min_rows, env_i64("CUDF_AMD_GB_ONE_TABLE_MIN_ROWS", int64_t{1} << 17));
-  e.estimate_min_rows = env_i64("CUDF_AMD_GB_ESTIMATE_MIN_ROWS", 1 << 16);
-  e.forced_p          = env_i64("CUDF_AMD_GB_P", 0);
-  e.s_items           = env_i64("CUDF_AMD_GB_S_ITEMS", 1024);
-  e.preagg_min_pct    = env_i64("CUDF_AMD_GB_PREAGG_MIN_PCT", 90);
-  e.dense_log2p       = env_i64("CUDF_AMD_GB_DENSE_LOG2P", 0);
-  e.scatter_block     = env_i64("CUDF_AMD_GB_SCATTER_BLOCK", 1024);
-  e.rpt               = env_i64("CUDF_AMD_GB_RPT", 8);
-  e.dense_nsplit      = env_i64("CUDF_AMD_GB_DENSE_NSPLIT", -1);
-  e.wc_g              = env_i64("CUDF_AMD_GB_WC_G", -1);
-  e.slices            = env_i64("CUDF_AMD_GB_SLICES", -1);
-  e.plan_load_pct     = env_i64("CUDF_AMD_GB_PLAN_LOAD_PCT", -1);
-  e.dense             = env_i64("CUDF_AMD_GB_DENSE", 1) != 0;
-  e.dense_composite   = env_i64("CUDF_AMD_GB_DENSE_COMPOSITE", 1) != 0;
-  e.dense_one_table   = env_i64("CUDF_AMD_GB_DENSE_ONE_TABLE", 1) != 0;
-  e.dense_ring        = env_i64("CUDF_AMD_GB_DENSE_RING", 1) != 0;
-  e.dense_multi       = env_i64("CUDF_AMD_GB_DENSE_MULTI", 1) != 0;
-  e.hot               = env_i64("CUDF_AMD_GB_HOT", 1) != 0;
-  e.preagg            = env_i64("CUDF_AMD_GB_PREAGG", 1) != 0;
-  e.optimistic        = env_i64("CUDF_AMD_GB_OPTIMISTIC", 1) != 0;
-  e.optimistic2       = env_i64("CUDF_AMD_GB_OPTIMISTIC2", 1) != 0;
-  e.exact             = env_i64("CUDF_AMD_GB_EXACT", 0) != 0;
-  e.wc                = env_i64("CUDF_AMD_GB_WC", 1) != 0;
-  e.cyclic            = env_i64("CUDF_AMD_GB_CYCLIC", 1) != 0;
-  e.stamps            = env_i64("CUDF_AMD_GB_STAMPS", 0) != 0;
-  e.debug             = env_i64("CUDF_AMD_DEBUG", 0) != 0;
-  e.no_simple         = env_i64("CUDF_AMD_GB_NO_SIMPLE", 0) != 0;
-  e.collapse_runs     = env_i64("CUDF_AMD_GB_COLLAPSE_RUNS", 1) != 0;
-  e.vec16             = env_i64("CUDF_AMD_GB_VEC16", 0) != 0;
-  e.trace             = env_i64("CUDF_AMD_GB_TRACE", 0) != 0;
-  // (off by default: measured SLOWER than the write-combining scatter + tagged tables - profiles/r3_sparse_ring.txt)
-  e.static_shapes     = env_i64("CUDF_AMD_GB_STATIC_SHAPES", 2);
+  e.one_table_min_rows = std::min(e.big_min_rows, int64_t{1} << 17);
+  e.dense_log2p        = env_i64("CUDF_AMD_GB_DENSE_LOG2P", 0);
+  e.dense_nsplit       = env_i64("CUDF_AMD_GB_DENSE_NSPLIT", -1);
+  e.dense              = env_i64("CUDF_AMD_GB_DENSE", 1) != 0;
+  e.dense_one_table    = env_i64("CUDF_AMD_GB_DENSE_ONE_TABLE", 1) != 0;
+  e.dense_ring         = env_i64("CUDF_AMD_GB_DENSE_RING", 1) != 0;
+  e.dense_multi        = env_i64("CUDF_AMD_GB_DENSE_MULTI", 1) != 0;
+  e.preagg             = env_i64("CUDF_AMD_GB_PREAGG", 1) != 0;
+  e.optimistic2        = env_i64("CUDF_AMD_GB_OPTIMISTIC2", 1) != 0;
+  e.collapse_runs      = env_i64("CUDF_AMD_GB_COLLAPSE_RUNS", 1) != 0;
+  e.arg_lookup         = env_i64("CUDF_AMD_GB_ARG_LOOKUP", 1) != 0;
+  e.debug              = env_i64("CUDF_AMD_DEBUG", 0) != 0;
+  e.trace              = env_i64("CUDF_AMD_GB_TRACE", 0) != 0;
   return e;
 }
 
@@ -406,7 +378,7 @@ void plan_accumulators(host_plan& hp, std::span<aggregation_request const> reque
       hp.key_acc[c] = find_or_add_acc(p, acc_desc{ANY_U64, SRC_VALUE, static_cast<int8_t>(hp.key_raw_vidx[c]), -1});
 }
 
-void plan_fast_path(host_plan& hp, planner_env const& env, bool need_rowid)
+void plan_fast_path(host_plan& hp, bool need_rowid)
 {
   auto& p = hp.dev;
   // ---- fast path: all units are plain 8-byte columns (no nulls, no conversion, no normalisation)
@@ -421,23 +393,17 @@ void plan_fast_path(host_plan& hp, planner_env const& env, bool need_rowid)
     if (!plain) { p.simple = 0; break; }
     p.simple_base[w] = static_cast<uint64_t const*>(c.head) + c.offset;
   }
-  if (env.no_simple || need_rowid) p.simple = 0;
-  p.simple_vec16 = p.simple;
-  for (int w = 0; p.simple && w < p.KU + p.NPAY; ++w)
-    if (reinterpret_cast<uintptr_t>(p.simple_base[w]) % 16 != 0) p.simple_vec16 = 0;
-  // measured slower than 8-byte loads in both the histogram (1.85 vs 1.6 ms) and the scatter (25.5M vs 22.2M
-  // cycles per workgroup): opt-in only
-  if (!env.vec16) p.simple_vec16 = 0;
+  if (need_rowid) p.simple = 0;
 }
 }  // namespace
 
-host_plan build_plan(table_view const& keys, null_policy policy, std::span<aggregation_request const> requests, planner_env const& env)
+host_plan build_plan(table_view const& keys, null_policy policy, std::span<aggregation_request const> requests)
 {
   host_plan hp;
   auto const needs = plan_columns(hp, keys, policy, requests);
   plan_units(hp, needs);
   plan_accumulators(hp, requests);
-  plan_fast_path(hp, env, needs.rowid);
+  plan_fast_path(hp, needs.rowid);
   return hp;
 }
 

@@ -5,6 +5,7 @@
 // retrieve_impl.cuh:169-222 (probe entry), size_impl.cuh:26-61 (size), join_utils.cu:45-221 (trivial left join,
 // full-join complement), join_common_utils.hpp:25-32 (load-factor check).
 #include "engine.hpp"
+#include "../common/env.hpp"
 #include "../common/profiler.hpp"
 
 #include <cudf/join/hash_join.hpp>
@@ -110,12 +111,6 @@ uint64_t const* key_bytes(column_view const& c, int width)
   return reinterpret_cast<uint64_t const*>(c.head<uint8_t>() + static_cast<std::size_t>(c.offset()) * static_cast<std::size_t>(width));
 }
 
-int64_t env_flag(char const* name, int64_t dflt)
-{
-  char const* v = std::getenv(name);
-  return v ? std::atoll(v) : dflt;
-}
-
 template <typename T>
 struct dev_scalar {  // one T in device memory, stream ordered
   rmm::device_buffer buf;
@@ -161,7 +156,7 @@ class hash_join_impl {
     // and a multiset walk ends at the first empty slot: 2.5 slots at load 0.5, 1.4 at 0.25 - so the table is kept
     // at <= 0.25 unless that would take more than 1/8 of the device memory (build_classic).
     // 8-byte slots {hash tag | row}, direct windowed probe. (The sliced table with inline keys and a radix-partitioned probe side
-    // of rounds 1-3 - CUDF_AMD_JOIN_PARTITIONED - was superseded by the LDS radix join and removed in round 4.)
+    // of rounds 1-3 was superseded by the LDS radix join and removed in round 4.)
     bool const build_check_nulls = _has_nulls && cudf::has_nulls(right);
     bool const key64 = is_single64(right) && (!build_check_nulls || _nulls_equal != null_equality::EQUAL);
     // (one 4-byte integer key: only the partitioned joins take it - they widen it in their first scatter level; everything else
@@ -179,7 +174,7 @@ class hash_join_impl {
     _classic_load = load_factor;
     // Dense build keys (one 8-byte integer key column, NULLs never match, valid values within a small range): a direct-address
     // table over [min, max] replaces the hash table - see engine.hpp. Decided from the exact minimum / maximum of the build keys.
-    if (_keyw != 0 && !_pack2 && !_kw2 && _key_class == 0 && rows >= static_cast<uint64_t>(env_flag("CUDF_AMD_JOIN_DENSE_MIN_ROWS", 1 << 16)) && env_flag("CUDF_AMD_JOIN_DENSE", 1) != 0) {
+    if (_keyw != 0 && !_pack2 && !_kw2 && _key_class == 0 && rows >= static_cast<uint64_t>(env_i64("CUDF_AMD_JOIN_DENSE_MIN_ROWS", 1 << 16)) && env_i64("CUDF_AMD_JOIN_DENSE", 1) != 0) {
       hipStream_t const s = stream.value();
       auto tmp            = cudf::get_current_device_resource_ref();
       bool const is_signed = class_of(right.column(0).type().id()) == CLS_SINT;
@@ -255,7 +250,7 @@ class hash_join_impl {
   void build_classic(stream_ref stream) const
   {
     auto const rows     = static_cast<uint64_t>(_right.num_rows());
-    double const target_load = std::min(_classic_load, 0.01 * static_cast<double>(env_flag("CUDF_AMD_JOIN_MAX_LOAD_PCT", 25)));
+    double const target_load = std::min(_classic_load, 0.25);
     uint64_t capacity = static_cast<uint64_t>(std::ceil(static_cast<double>(rows) / target_load));
     if (capacity * 8 > (uint64_t{36} << 30)) capacity = static_cast<uint64_t>(std::ceil(static_cast<double>(rows) / _classic_load));
     capacity          = std::clamp<uint64_t>(capacity, rows + 1, (uint64_t{1} << 32) - 2);  // always one empty slot
@@ -277,7 +272,7 @@ class hash_join_impl {
   // radix_scatter_args::pack): the exact minimum / maximum of both build columns decide (two passes over the build keys, one read-back).
   void decide_packed_words(table_view const& right, stream_ref stream)
   {
-    if (env_flag("CUDF_AMD_JOIN_PACK_RANGE", 1) == 0 || right.num_rows() < 2) return;
+    if (env_i64("CUDF_AMD_JOIN_PACK_RANGE", 1) == 0 || right.num_rows() < 2) return;
     for (int c = 0; c < 2; ++c) {
       auto const cls = class_of(right.column(c).type().id());
       if (cls != CLS_SINT && cls != CLS_UINT) return;
@@ -430,16 +425,14 @@ class hash_join_impl {
   }
   bool try_radix_build(table_view const& right, stream_ref stream)
   {
-    if (env_flag("CUDF_AMD_JOIN_RADIX", 1) == 0) return false;
     auto const& col     = right.column(0);
     int64_t const rows  = right.num_rows();
     // (two packed columns: the rows with a NULL in either are dropped; their number is at least the larger of the two null counts)
     int64_t const valid = rows - std::max<int64_t>(col.nullable() ? col.null_count() : 0, ((_pack2 || _kw2) && right.column(1).nullable()) ? right.column(1).null_count() : 0);
     // partitions: a power of two with at most ~3500 build rows each (LDS tables of 8192 slots: load <= 0.43), 128 x (16 ... 256)
-    int64_t const part_rows = std::clamp<int64_t>(env_flag("CUDF_AMD_JOIN_RADIX_PART_ROWS", 3500), 256, 3500);
     int64_t nparts = 2048;
-    while (nparts < (two_words() ? 16384 : 32768) && valid > nparts * part_rows) nparts <<= 1;  // (two-word keys: second-level rings of at least 32 slots)
-    if (valid < env_flag("CUDF_AMD_JOIN_RADIX_MIN_BUILD", 3 << 20) || valid > nparts * 3500) return false;
+    while (nparts < (two_words() ? 16384 : 32768) && valid > nparts * 3500) nparts <<= 1;  // (two-word keys: second-level rings of at least 32 slots)
+    if (valid < env_i64("CUDF_AMD_JOIN_RADIX_MIN_BUILD", 3 << 20) || valid > nparts * 3500) return false;
     _rx_nparts = static_cast<int32_t>(nparts);
     hipStream_t const s = stream.value();
     if (!radix_partition(key_bytes(col, _keyw), (_has_nulls && col.has_nulls()) ? col.null_mask() : nullptr, col.offset(), rows, valid, _rx_build, stream, _mr,
@@ -477,7 +470,7 @@ class hash_join_impl {
     if (left_join && (_pack2 || _kw2) && (probe_nulls || second_nulls)) return std::nullopt;
     int64_t const rows  = left.num_rows();
     int64_t const valid = rows - std::max<int64_t>(col.nullable() ? col.null_count() : 0, second_nulls ? left.column(1).null_count() : 0);
-    if (rows < env_flag("CUDF_AMD_JOIN_RADIX_MIN_PROBE", 8 << 20) || rows > (int64_t{1} << 31) - 1) return std::nullopt;
+    if (rows < env_i64("CUDF_AMD_JOIN_RADIX_MIN_PROBE", 8 << 20) || rows > (int64_t{1} << 31) - 1) return std::nullopt;
     hipStream_t const s = stream.value();
     auto tmp            = cudf::get_current_device_resource_ref();
     radix_side probe;
@@ -557,15 +550,14 @@ class hash_join_impl {
     auto tmp            = cudf::get_current_device_resource_ref();
     auto log2c = [](uint64_t v) { int l = 0; while ((uint64_t{1} << l) < v) ++l; return l; };
     // slices of >= 1 MB (CUDF_AMD_JOIN_DENSE_PART_SLICE_LOG2: keys per slice, the tests shrink it), at most 256 of them
-    int const shift     = std::max(static_cast<int>(env_flag("CUDF_AMD_JOIN_DENSE_PART_SLICE_LOG2", 18)), log2c(_dense_range) - 8);
+    int const shift     = std::max(static_cast<int>(env_i64("CUDF_AMD_JOIN_DENSE_PART_SLICE_LOG2", 18)), log2c(_dense_range) - 8);
     int64_t const P     = static_cast<int64_t>((_dense_range - 1) >> shift) + 1;
     int64_t Pring = 16;
     while (Pring < P) Pring <<= 1;
-    // CUDF_AMD_JOIN_DENSE_PART_BLOCK=512: two workgroups of 512 threads per CU (8192 ring slots each) instead of one of 1024 - measured
-    // 8 % slower on C3 (1.73 against 1.60 ms for both scatters), kept for the record (profiles/r3_c3_dense_part.txt)
-    int64_t const rpt   = env_flag("CUDF_AMD_JOIN_DENSE_PART_RPT", 4) == 8 ? 8 : 4;
-    int64_t const block = env_flag("CUDF_AMD_JOIN_DENSE_PART_BLOCK", 1024) == 512 ? 512 : 1024, tile_rows = block * (block == 1024 ? rpt : 4);
-    int64_t const tiles = (nrows + tile_rows - 1) / tile_rows, S = std::clamp<int64_t>(tiles, 1, block == 512 ? 512 : 256);
+    // one workgroup of 1024 threads per CU, tiles of 4096 rows (two workgroups of 512 threads per CU measured 8 % slower on C3: 1.73
+    // against 1.60 ms for both scatters, profiles/r3_c3_dense_part.txt)
+    int64_t const tile_rows = 4 * 1024;
+    int64_t const tiles = (nrows + tile_rows - 1) / tile_rows, S = std::clamp<int64_t>(tiles, 1, 256);
     double const mean   = static_cast<double>(std::min<int64_t>(nrows, (tiles + S - 1) / S * tile_rows)) / static_cast<double>(P);
     int64_t const cap   = (static_cast<int64_t>(mean * 1.02 + 6.0 * std::sqrt(std::max(mean, 1.0)) + 64.0) + 31) / 32 * 32;
     out.recs   = rmm::device_buffer{static_cast<std::size_t>(Pring * S * cap) * sizeof(uint64_t), s, tmp};
@@ -586,9 +578,7 @@ class hash_join_impl {
     a.mask_offset    = mask_offset;
     a.nrows          = nrows;
     a.P              = static_cast<int32_t>(Pring);
-    a.capl           = (block == 512 ? 13 : 14) - log2c(static_cast<uint64_t>(Pring));  // 16384 (8192) ring slots of 8 bytes
-    a.block          = static_cast<int32_t>(block);
-    a.rpt            = static_cast<int32_t>(rpt);
+    a.capl           = 14 - log2c(static_cast<uint64_t>(Pring));  // 16384 ring slots of 8 bytes
     a.shift          = shift;
     a.slices         = static_cast<int32_t>(S);
     a.out_key        = static_cast<uint64_t*>(out.recs.data());
@@ -621,8 +611,8 @@ class hash_join_impl {
   {
     auto const& col    = right.column(0);
     int64_t const rows = right.num_rows();
-    if (env_flag("CUDF_AMD_JOIN_DENSE_PART", 1) == 0 || rows < env_flag("CUDF_AMD_JOIN_DENSE_PART_MIN_BUILD", 4 << 20) ||
-        static_cast<int64_t>(_dense_range) < env_flag("CUDF_AMD_JOIN_DENSE_PART_MIN_RANGE", 8 << 20) || rows > (int64_t{1} << 31) - 1)
+    if (rows < env_i64("CUDF_AMD_JOIN_DENSE_PART_MIN_BUILD", 4 << 20) ||
+        static_cast<int64_t>(_dense_range) < env_i64("CUDF_AMD_JOIN_DENSE_PART_MIN_RANGE", 8 << 20) || rows > (int64_t{1} << 31) - 1)
       return false;
     hipStream_t const s = stream.value();
     auto tmp            = cudf::get_current_device_resource_ref();
@@ -656,7 +646,7 @@ class hash_join_impl {
     bool const probe_nulls = _has_nulls && col.has_nulls();
     int64_t const rows     = left.num_rows();
     if (single_int_width(left) != _keyw || _keyw == 0 || (probe_nulls && _nulls_equal == null_equality::EQUAL) ||
-        rows < env_flag("CUDF_AMD_JOIN_DENSE_ORDERED_MIN_PROBE", 1 << 20) || rows + row_base > (int64_t{1} << 31) - 1)
+        rows < env_i64("CUDF_AMD_JOIN_DENSE_ORDERED_MIN_PROBE", 1 << 20) || rows + row_base > (int64_t{1} << 31) - 1)
       return std::nullopt;
     hipStream_t const s = stream.value();
     auto tmp            = cudf::get_current_device_resource_ref();
@@ -711,7 +701,7 @@ class hash_join_impl {
     bool const probe_nulls = _has_nulls && col.has_nulls();
     int64_t const rows     = left.num_rows();
     if (single_int_width(left) != _keyw || (probe_nulls && _nulls_equal == null_equality::EQUAL) ||
-        rows < env_flag("CUDF_AMD_JOIN_DENSE_PART_MIN_PROBE", 8 << 20) || rows > (int64_t{1} << 31) - 1)
+        rows < env_i64("CUDF_AMD_JOIN_DENSE_PART_MIN_PROBE", 8 << 20) || rows > (int64_t{1} << 31) - 1)
       return std::nullopt;
     hipStream_t const s = stream.value();
     auto tmp            = cudf::get_current_device_resource_ref();
@@ -875,7 +865,7 @@ class hash_join_impl {
     // FULL join (round 4): the LEFT join of the partitioned paths (radix partitions, dense unique table) + the build rows nobody
     // matched - marked from the left join's build indices, appended by the complement kernel of the table path (reference
     // hash_join.cu full-join complement, join_utils.cu:45-221)
-    if (k == 2 && env_flag("CUDF_AMD_JOIN_FULL_PARTITIONED", 1) != 0) {
+    if (k == 2) {
       if (auto r = probe_partitioned_paths(left, 1, stream, cudf::get_current_device_resource_ref(), row_base); r.has_value()) {
         auto full = full_from_left(std::move(*r), stream, mr);
         if (output_size.has_value())
@@ -949,7 +939,7 @@ class hash_join_impl {
     }
     // a dense unique table. CUDF_AMD_JOIN_DENSE_PROBE: 1 (default) inner joins by the ordered direct probe (pairs in probe-row
     // order), 2 by probe rows partitioned by key range (~0.6 ms less at C3, pairs partition-major), 0 neither; left joins in one pass
-    int64_t dense_probe     = env_flag("CUDF_AMD_JOIN_DENSE_PROBE", -1);
+    int64_t dense_probe     = env_i64("CUDF_AMD_JOIN_DENSE_PROBE", -1);
     bool const unique_table = (_dense && !_dense_has_dups) || _dense_part;
     if (dense_probe < 0) {
       // The ordered direct probe pays one random access into the table per probe key INSIDE the table's range (a key outside is
@@ -957,9 +947,9 @@ class hash_join_impl {
       // probe rows partitioned by key range (L2-local lookups) take 6.0 ms + the pairs partition-major (profiles/r4_c3_inrange.txt).
       // A strided sample of the probe keys decides; the table must be large enough for the partitions to matter.
       dense_probe = 1;
-      if (_dense_part && k == 0 && left.num_rows() >= env_flag("CUDF_AMD_JOIN_DENSE_PART_MIN_PROBE", 8 << 20) && single_int_width(left) == _keyw) {
+      if (_dense_part && k == 0 && left.num_rows() >= env_i64("CUDF_AMD_JOIN_DENSE_PART_MIN_PROBE", 8 << 20) && single_int_width(left) == _keyw) {
         double const share = dense_inrange_share(left, stream);
-        if (share > 0.01 * static_cast<double>(env_flag("CUDF_AMD_JOIN_DENSE_PART_INRANGE_PCT", 55))) dense_probe = 2;
+        if (share > 0.55) dense_probe = 2;
       }
     }
     if (unique_table && k == 0 && dense_probe == 1) {
@@ -1004,7 +994,7 @@ class hash_join_impl {
     auto const& col        = left.column(0);
     bool const probe_nulls = _has_nulls && col.has_nulls();
     if (single_int_width(left) != _keyw || _keyw == 0 || (probe_nulls && _nulls_equal == null_equality::EQUAL) ||
-        left.num_rows() < env_flag("CUDF_AMD_JOIN_DENSE_ORDERED_MIN_PROBE", 1 << 20) || left.num_rows() + row_base > (int64_t{1} << 31) - 1)
+        left.num_rows() < env_i64("CUDF_AMD_JOIN_DENSE_ORDERED_MIN_PROBE", 1 << 20) || left.num_rows() + row_base > (int64_t{1} << 31) - 1)
       return std::nullopt;
     hipStream_t const s = stream.value();
     std::size_t const n = static_cast<std::size_t>(left.num_rows());

@@ -692,8 +692,7 @@ void launch_radix_scatter(radix_scatter_args const& a, radix_scatter_args* d_arg
   static std::once_flag attr_once;
   std::call_once(attr_once, [] {
     for (void const* fn : {reinterpret_cast<void const*>(&k_radix_scatter<1, 4, 2, false>), reinterpret_cast<void const*>(&k_radix_scatter<2, 4, 2, false>),
-                           reinterpret_cast<void const*>(&k_radix_scatter<1, 4, 2, true>), reinterpret_cast<void const*>(&k_radix_scatter<1, 4, 2, true, 512>),
-                           reinterpret_cast<void const*>(&k_radix_scatter<1, 8, 2, true>), reinterpret_cast<void const*>(&k_radix_scatter<1, 2, 2, false, 1024, 2>),
+                           reinterpret_cast<void const*>(&k_radix_scatter<1, 4, 2, true>), reinterpret_cast<void const*>(&k_radix_scatter<1, 2, 2, false, 1024, 2>),
                            reinterpret_cast<void const*>(&k_radix_scatter<2, 2, 2, false, 1024, 2>),
                            reinterpret_cast<void const*>(&k_radix_scatter<1, 4, 2, false, 1024, 1, SHAPE_INT64>),
                            reinterpret_cast<void const*>(&k_radix_scatter<1, 4, 2, true, 1024, 1, SHAPE_INT64>),
@@ -724,9 +723,7 @@ void launch_radix_scatter(radix_scatter_args const& a, radix_scatter_args* d_arg
     }
   }
   cudf::detail::prof::scope prof_{a.level == 1 ? "join_partition" : "join_partition_level2", stream};
-  if (dense && a.block == 512) hipLaunchKernelGGL((k_radix_scatter<1, 4, 2, true, 512>), dim3(a.slices), dim3(512), lds, stream, d_args);
-  else if (dense && a.rpt == 8) hipLaunchKernelGGL((k_radix_scatter<1, 8, 2, true>), dim3(a.slices), dim3(1024), lds, stream, d_args);
-  else if (dense && shape == SHAPE_INT64) hipLaunchKernelGGL((k_radix_scatter<1, 4, 2, true, 1024, 1, SHAPE_INT64>), dim3(a.slices), dim3(1024), lds, stream, d_args);
+  if (dense && shape == SHAPE_INT64) hipLaunchKernelGGL((k_radix_scatter<1, 4, 2, true, 1024, 1, SHAPE_INT64>), dim3(a.slices), dim3(1024), lds, stream, d_args);
   else if (dense) hipLaunchKernelGGL((k_radix_scatter<1, 4, 2, true>), dim3(a.slices), dim3(1024), lds, stream, d_args);
   else if (shape == SHAPE_TWO88) hipLaunchKernelGGL((k_radix_scatter<1, 2, 2, false, 1024, 2, SHAPE_TWO88>), dim3(a.slices), dim3(1024), lds, stream, d_args);
   else if (shape == SHAPE_TWO84) hipLaunchKernelGGL((k_radix_scatter<1, 2, 2, false, 1024, 2, SHAPE_TWO84>), dim3(a.slices), dim3(1024), lds, stream, d_args);

@@ -2,6 +2,8 @@
 // Host runtime behind the boundary types: memory resources, streams, errors, views and owning
 // column/table. Reference counterparts: cpp/src/column/column_view.cpp, column.cu, table/table.cpp,
 // table_view.cpp, utilities/default_stream.cpp:39 — restated from their documented behaviour for HIP.
+#include "../common/env.hpp"
+
 #include <cudf/column/column.hpp>
 #include <cudf/null_mask.hpp>
 #include <cudf/table/table.hpp>
@@ -418,11 +420,7 @@ void pool_memory_resource::do_deallocate(void* p, std::size_t, hipStream_t strea
   // Bound what the cache may hold (every distinct rounded size keeps its own list): beyond the limit
   // (CUDF_AMD_POOL_MAX_CACHED_GB, default 128 of the 288 GB) the least recently returned blocks go back to the
   // driver first, so a caller that changes its shapes does not lose the blocks of its current working set.
-  static std::size_t const limit = [] {
-    char const* e = std::getenv("CUDF_AMD_POOL_MAX_CACHED_GB");
-    std::size_t const gb = (e != nullptr && *e != 0) ? std::strtoull(e, nullptr, 10) : 128;
-    return gb << 30;
-  }();
+  std::size_t const limit = static_cast<std::size_t>(cudf::detail::env_i64("CUDF_AMD_POOL_MAX_CACHED_GB", 128)) << 30;
   while (_impl->cached > limit) {
     std::vector<impl::block>* oldest_list = nullptr;
     std::size_t oldest_idx = 0;
