@@ -491,7 +491,10 @@ flat_table flatten(table_view const& input, uint64_t with_validity, hipStream_t 
     f.cols.push_back(column_view{data_type{type_id::UINT8}, col.size(), f.temps.back().data(), nullptr, 0, 0});
     f.validity_of.push_back(c);
   }
-  CUDF_EXPECTS(static_cast<int>(f.cols.size()) <= MAX_COLS, "distributed shuffle: too many columns (limit 16 including validity columns)");
+  CUDF_EXPECTS(static_cast<int>(f.cols.size()) <= MAX_COLS,
+               "distributed shuffle: at most 16 flat columns (a column with nulls on any rank counts twice: its validity travels as a "
+               "byte column)",
+               std::invalid_argument);
   return f;
 }
 // buffers of the flat columns (nrows rows each) -> owning table with the input's types and re-packed validity
@@ -718,7 +721,11 @@ std::unique_ptr<table> shuffle_body(table_view const& input, std::vector<size_ty
   int const N = comm.size(), me = comm.rank();
   transport& link = comm.link();
   auto tmp        = cudf::get_current_device_resource_ref();
-  CUDF_EXPECTS(input.num_columns() >= 1 && input.num_columns() < 60, "shuffle: 1 to 59 columns", std::invalid_argument);
+  // (the exact limit - 16 flat columns, a column with nulls on any rank counting twice - is known after round 0; flatten checks it
+  // on every rank with the same verdict)
+  CUDF_EXPECTS(input.num_columns() >= 1 && input.num_columns() <= MAX_COLS,
+               "shuffle: 1 to 16 flat columns (a column with nulls on any rank counts twice: its validity travels as a byte column)",
+               std::invalid_argument);
   auto const hashed = input.select(key_columns);
   CUDF_EXPECTS(hashed.num_columns() >= 1, "shuffle: at least one key column", std::invalid_argument);
 

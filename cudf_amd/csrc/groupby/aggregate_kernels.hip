@@ -99,10 +99,10 @@ __global__ void __launch_bounds__(256) k_finalize(finalize_args const* __restric
           bits                = d.kind == OUT_SUMOV_SUM ? static_cast<uint64_t>(wrap) : static_cast<uint64_t>(overflow);
           if (!valid) bits = 0;
         } else if (d.kind == OUT_MEAN) {
-          // MEAN = double(SUM) / COUNT_VALID as FLOAT64 (reference hash_compound_agg_finalizer.cu:92-133)
+          // MEAN = double(SUM) / COUNT_VALID as FLOAT64 (reference hash_compound_agg_finalizer.cu:92-133); the SUM of every integer
+          // source, unsigned ones included, is INT64 (aggregation.hpp:949-954), so a wrapped uint64 sum divides as a signed value
           double const s = d.cls == cudf::detail::CLS_F64 ? __longlong_as_double(static_cast<long long>(a0))
-                           : d.cls == cudf::detail::CLS_UINT ? static_cast<double>(a0)
-                                                             : static_cast<double>(static_cast<int64_t>(a0));
+                                                          : static_cast<double>(static_cast<int64_t>(a0));
           double const n = static_cast<double>(static_cast<int64_t>(rec[p.KU + d.a1]));
           bits           = static_cast<uint64_t>(__double_as_longlong(valid ? s / n : 0.0));
         } else {  // OUT_ACC: accumulator class -> output type

@@ -82,13 +82,16 @@ std::pair<std::unique_ptr<table>, std::vector<size_type>> range_partition(
   stream_ref stream = get_default_stream(), rmm::device_async_resource_ref mr = get_current_device_resource_ref());
 
 // Every rank passes its local rows; every rank receives the rows whose keys it owns (from rank 0, then rank 1, ...).
-// Collective: all ranks of the communicator must call it, with tables of the same column types.
+// Collective: all ranks of the communicator must call it, with tables of the same column types. At most 16 FLAT columns travel: every
+// input column is one, and a column that has nulls on any rank adds one more (its validity travels as a byte column); beyond that
+// every rank raises std::invalid_argument before the payload exchange.
 std::unique_ptr<table> shuffle(table_view const& input, std::vector<size_type> const& key_columns, communicator& comm,
                                stream_ref stream = get_default_stream(),
                                rmm::device_async_resource_ref mr = get_current_device_resource_ref());
 
 // BASELINE config 5: shuffle the rows of (keys, request value columns) by key, then the local hash groupby. The groups
-// of different ranks are disjoint: the union of the ranks' results is the global result, no merge step.
+// of different ranks are disjoint: the union of the ranks' results is the global result, no merge step. The key columns and each
+// distinct value column travel through `shuffle`, so they count toward its 16 flat columns.
 std::pair<std::unique_ptr<table>, std::vector<groupby::aggregation_result>> shuffle_groupby(
   table_view const& keys, std::span<groupby::aggregation_request const> requests, communicator& comm,
   null_policy null_handling = null_policy::EXCLUDE, stream_ref stream = get_default_stream(),
@@ -102,7 +105,11 @@ std::pair<std::unique_ptr<table>, std::vector<groupby::aggregation_result>> shuf
 // products), and the finalisation after the merge (counts back to INT32, MEAN = merged sum / merged count, NULL where no valid value
 // arrived). Same result types and nullability as groupby::aggregate on the union of the ranks' rows; the ranks' results are disjoint.
 // Aggregations that do not decompose this way (M2 / VARIANCE / STD, ARGMIN / ARGMAX, SUM_WITH_OVERFLOW, MEAN of a decimal or duration
-// column) raise std::invalid_argument on every rank before anything is exchanged. Collective.
+// column) raise std::invalid_argument on every rank before anything is exchanged. The key columns and every request's partial
+// columns (MEAN: sum + count, shared with a SUM of the same request) travel through `shuffle` and count toward its 16 flat columns;
+// a partial that is NULL for some group on any rank (SUM / PRODUCT / SUM_OF_SQUARES / MIN / MAX of a column with nulls) counts
+// twice. The merge groupby on the owner takes every partial column as a value column of its own, so the partials of all requests
+// (plus any float key column) meet the hash groupby's limit of 7 distinct value columns there. Collective.
 std::pair<std::unique_ptr<table>, std::vector<groupby::aggregation_result>> combine_groupby(
   table_view const& keys, std::span<groupby::aggregation_request const> requests, communicator& comm,
   null_policy null_handling = null_policy::EXCLUDE, stream_ref stream = get_default_stream(),

@@ -960,3 +960,20 @@ def test_argmin_argmax_by_lookup(G, oracle, monkeypatch, ktype, vtype, include):
             for kind, a, b in zip(kinds, ra, rb):
                 if kind != "sum":  # (float sums: order-dependent; the oracle comparison above bounds them)
                     kat.compare_columns(a, b, f"lookup against the engine [{kind}]")
+
+
+@pytest.mark.parametrize("n", [64, 200_000])
+def test_mean_of_uint64_divides_the_int64_sum(G, oracle, n):
+    """MEAN of a uint64 column whose group sums pass 2^63: SUM of an integer column is INT64 (reference aggregation.hpp:949-954)
+    and MEAN divides that sum, so a wrapped sum gives a negative mean, as the engine's own SUM column says (the finalisation once
+    divided the sum of an unsigned source as uint64)."""
+    from oracle.oracle import HostColumn
+    rng = np.random.default_rng(n)
+    k = rng.integers(0, max(2, n // 16), n).astype(np.int64)
+    v = HostColumn(rng.integers(2**62, 2**64, n, dtype=np.uint64), rng.random(n) > 0.1, "uint64")
+    got = kat.sort_groups(*G.groupby([k], [(v, ["sum", "mean", "count_valid"])]))
+    exp = kat.sort_groups(*oracle.groupby([k], [(v, ["sum", "mean", "count_valid"])]))
+    kat.compare_columns(got[0][0], exp[0][0], "keys")
+    assert (exp[1][0][1][0] < 0).any(), "some group sum wraps"
+    for a, e, name in zip(got[1][0], exp[1][0], ["sum", "mean", "count"]):
+        kat.compare_columns(a, e, name)
