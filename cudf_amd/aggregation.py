@@ -2,7 +2,7 @@
 Kind values are those of cudf::aggregation::Kind (cpp/include/cudf/aggregation.hpp:78-121)."""
 from enum import IntEnum
 
-from .types import NullPolicy
+from .types import NullOrder, NullPolicy, Order
 
 
 class Kind(IntEnum):
@@ -26,6 +26,9 @@ class Kind(IntEnum):
     ARGMIN = 17
     NUNIQUE = 18
     NTH_ELEMENT = 19
+    ROW_NUMBER = 20
+    EWMA = 21
+    RANK = 22
 
 
 class Interpolation(IntEnum):  # cudf::interpolation (reference cpp/include/cudf/types.hpp:173-180)
@@ -35,6 +38,25 @@ class Interpolation(IntEnum):  # cudf::interpolation (reference cpp/include/cudf
     MIDPOINT = 3
     NEAREST = 4
     NEAREST_HALF_UP = 5
+
+
+class RankMethod(IntEnum):  # cudf::rank_method (reference cpp/include/cudf/aggregation.hpp:37-43)
+    FIRST = 0
+    AVERAGE = 1
+    MIN = 2
+    MAX = 3
+    DENSE = 4
+
+
+class RankPercentage(IntEnum):  # cudf::rank_percentage (aggregation.hpp:50-54)
+    NONE = 0
+    ZERO_NORMALIZED = 1
+    ONE_NORMALIZED = 2
+
+
+class ReplacePolicy(IntEnum):  # cudf::replace_policy (reference cpp/include/cudf/replace.hpp:32)
+    PRECEDING = 0
+    FOLLOWING = 1
 
 
 class Aggregation:
@@ -131,3 +153,11 @@ def quantile(quantiles, interp: Interpolation = Interpolation.LINEAR):
 
 def m2():
     return Aggregation(Kind.M2)
+
+
+def rank(method: RankMethod, column_order: Order = Order.ASCENDING, null_handling: NullPolicy = NullPolicy.EXCLUDE,
+         null_precedence: NullOrder = NullOrder.AFTER, percentage: RankPercentage = RankPercentage.NONE):
+    # pylibcudf.aggregation.rank (aggregation.pyi; cudf::make_rank_aggregation, a scan kind only). The C ABI carries the method in
+    # params and column_order + 2 * null_precedence + 4 * null_handling + 8 * percentage in params2.
+    packed = int(column_order) + 2 * int(null_precedence) + 4 * int(null_handling) + 8 * int(percentage)
+    return Aggregation(Kind.RANK, int(RankMethod(method)), packed)

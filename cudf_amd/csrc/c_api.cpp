@@ -293,6 +293,77 @@ cudf_amd_status cudf_amd_groupby_aggregate(const cudf_amd_column_view* keys, int
   });
 }
 
+cudf_amd_status cudf_amd_groupby_scan(const cudf_amd_column_view* keys, int32_t num_keys, int32_t include_null_keys,
+                                      int32_t keys_are_sorted, const cudf_amd_aggregation_request* requests, int32_t num_requests,
+                                      void* stream, cudf_amd_table_t* out_keys, cudf_amd_table_t* out_results)
+{
+  return guarded([&] {
+    *out_keys    = nullptr;
+    *out_results = nullptr;
+    auto const kt = to_table(keys, num_keys);
+    std::vector<cudf::groupby::scan_request> reqs(num_requests);
+    for (int32_t r = 0; r < num_requests; ++r) {
+      reqs[r].values = to_view(requests[r].values);
+      for (int32_t k = 0; k < requests[r].num_kinds; ++k) {
+        if (requests[r].kinds[k] == cudf::aggregation::RANK) {
+          int32_t const method = requests[r].params ? requests[r].params[k] : 0;
+          int32_t const packed = requests[r].params2 ? requests[r].params2[k] : 0;
+          CUDF_EXPECTS(method >= 0 && method <= 4, "RANK: unknown rank_method.", std::invalid_argument);
+          CUDF_EXPECTS(packed >= 0 && (packed >> 3) <= 2, "RANK: unknown parameters.", std::invalid_argument);
+          reqs[r].aggregations.push_back(cudf::make_rank_aggregation<cudf::groupby_scan_aggregation>(
+            static_cast<cudf::rank_method>(method), (packed & 1) ? cudf::order::DESCENDING : cudf::order::ASCENDING,
+            (packed & 4) ? cudf::null_policy::INCLUDE : cudf::null_policy::EXCLUDE, (packed & 2) ? cudf::null_order::BEFORE : cudf::null_order::AFTER,
+            static_cast<cudf::rank_percentage>(packed >> 3)));
+          continue;
+        }
+        // the kinds that cannot scan have no groupby_scan_aggregation form (reference sort/scan.cpp:48)
+        auto a       = make_agg(requests[r], k);
+        auto* as_scan = dynamic_cast<cudf::groupby_scan_aggregation*>(a.get());
+        if (as_scan == nullptr) CUDF_FAIL("Unsupported groupby scan aggregation");
+        a.release();
+        reqs[r].aggregations.emplace_back(as_scan);
+      }
+    }
+    cudf::groupby::groupby gb{kt, include_null_keys ? cudf::null_policy::INCLUDE : cudf::null_policy::EXCLUDE,
+                              keys_are_sorted ? cudf::sorted::YES : cudf::sorted::NO};
+    auto [skeys, results] = gb.scan(reqs, cudf::stream_ref{as_stream(stream)});
+    auto kh               = std::make_unique<cudf_amd_table_s>();
+    kh->cols              = skeys->release();
+    auto rh               = std::make_unique<cudf_amd_table_s>();
+    for (auto& r : results)
+      for (auto& c : r.results) rh->cols.push_back(std::move(c));
+    *out_keys    = kh.release();
+    *out_results = rh.release();
+  });
+}
+
+cudf_amd_status cudf_amd_groupby_replace_nulls(const cudf_amd_column_view* keys, int32_t num_keys, int32_t include_null_keys,
+                                               int32_t keys_are_sorted, const cudf_amd_column_view* values, int32_t num_values,
+                                               const int32_t* policies, void* stream, cudf_amd_table_t* out_keys,
+                                               cudf_amd_table_t* out_values)
+{
+  return guarded([&] {
+    *out_keys   = nullptr;
+    *out_values = nullptr;
+    auto const kt = to_table(keys, num_keys);
+    auto const vt = to_table(values, num_values);
+    std::vector<cudf::replace_policy> pol;
+    for (int32_t i = 0; policies != nullptr && i < num_values; ++i) {
+      CUDF_EXPECTS(policies[i] == 0 || policies[i] == 1, "replace policy must be 0 (PRECEDING) or 1 (FOLLOWING)", std::invalid_argument);
+      pol.push_back(policies[i] ? cudf::replace_policy::FOLLOWING : cudf::replace_policy::PRECEDING);
+    }
+    cudf::groupby::groupby gb{kt, include_null_keys ? cudf::null_policy::INCLUDE : cudf::null_policy::EXCLUDE,
+                              keys_are_sorted ? cudf::sorted::YES : cudf::sorted::NO};
+    auto [skeys, filled] = gb.replace_nulls(vt, pol, cudf::stream_ref{as_stream(stream)});
+    auto kh              = std::make_unique<cudf_amd_table_s>();
+    kh->cols             = skeys->release();
+    auto vh              = std::make_unique<cudf_amd_table_s>();
+    vh->cols             = filled->release();
+    *out_keys   = kh.release();
+    *out_values = vh.release();
+  });
+}
+
 static cudf_amd_table_t indices_to_table(cudf::join_index_pair&& p)
 {
   auto t = std::make_unique<cudf_amd_table_s>();

@@ -90,6 +90,33 @@ class nunique_aggregation final : public groupby_aggregation, public reduce_aggr
   [[nodiscard]] std::unique_ptr<aggregation> clone() const override { return std::make_unique<nunique_aggregation>(*this); }
   null_policy _null_handling;
 };
+// RANK (reference detail/aggregation/aggregation.hpp:846-900): a scan kind only
+class rank_aggregation final : public groupby_scan_aggregation {
+ public:
+  rank_aggregation(rank_method method, order column_order, null_policy null_handling, null_order null_precedence, rank_percentage percentage)
+    : aggregation{aggregation::RANK}, _method{method}, _column_order{column_order}, _null_handling{null_handling},
+      _null_precedence{null_precedence}, _percentage{percentage}
+  {
+  }
+  [[nodiscard]] bool is_equal(aggregation const& other) const override
+  {
+    auto const* o = dynamic_cast<rank_aggregation const*>(&other);
+    return o != nullptr && aggregation::is_equal(other) && o->_method == _method && o->_column_order == _column_order &&
+           o->_null_handling == _null_handling && o->_null_precedence == _null_precedence && o->_percentage == _percentage;
+  }
+  [[nodiscard]] size_t do_hash() const override
+  {
+    return aggregation::do_hash() ^ std::hash<int>{}(static_cast<int>(_method) + 5 * static_cast<int>(_column_order) +
+                                                     10 * static_cast<int>(_null_handling) + 20 * static_cast<int>(_null_precedence) +
+                                                     40 * static_cast<int>(_percentage));
+  }
+  [[nodiscard]] std::unique_ptr<aggregation> clone() const override { return std::make_unique<rank_aggregation>(*this); }
+  rank_method _method;
+  order _column_order;
+  null_policy _null_handling;
+  null_order _null_precedence;
+  rank_percentage _percentage;
+};
 data_type target_type(data_type source, aggregation::Kind k);
 bool is_valid_aggregation(data_type source, aggregation::Kind k);
 }  // namespace cudf::detail

@@ -19,7 +19,7 @@ namespace cudf {
 // ---------------------------------------------------------------------------------------------------------
 // aggregation descriptors (reference cpp/src/aggregation/aggregation.cpp factories)
 namespace detail {
-class simple_aggregation final : public groupby_aggregation, public reduce_aggregation {
+class simple_aggregation final : public groupby_aggregation, public groupby_scan_aggregation, public reduce_aggregation {
  public:
   explicit simple_aggregation(aggregation::Kind k) : aggregation{k} {}
   [[nodiscard]] std::unique_ptr<aggregation> clone() const override
@@ -113,6 +113,23 @@ CUDF_AMD_FACTORY(make_argmax_aggregation, ARGMAX)
 CUDF_AMD_FACTORY(make_argmin_aggregation, ARGMIN)
 CUDF_AMD_FACTORY(make_median_aggregation, MEDIAN)
 #undef CUDF_AMD_FACTORY
+
+// the scan kinds (reference aggregation.cpp's groupby_scan_aggregation instantiations)
+template std::unique_ptr<groupby_scan_aggregation> make_sum_aggregation<groupby_scan_aggregation>();
+template std::unique_ptr<groupby_scan_aggregation> make_product_aggregation<groupby_scan_aggregation>();
+template std::unique_ptr<groupby_scan_aggregation> make_min_aggregation<groupby_scan_aggregation>();
+template std::unique_ptr<groupby_scan_aggregation> make_max_aggregation<groupby_scan_aggregation>();
+template std::unique_ptr<groupby_scan_aggregation> make_count_aggregation<groupby_scan_aggregation>(null_policy);
+
+template <typename Base>
+std::unique_ptr<Base> make_rank_aggregation(rank_method method, order column_order, null_policy null_handling, null_order null_precedence,
+                                            rank_percentage percentage)
+{
+  return std::make_unique<detail::rank_aggregation>(method, column_order, null_handling, null_precedence, percentage);
+}
+template std::unique_ptr<aggregation> make_rank_aggregation<aggregation>(rank_method, order, null_policy, null_order, rank_percentage);
+template std::unique_ptr<groupby_scan_aggregation> make_rank_aggregation<groupby_scan_aggregation>(rank_method, order, null_policy,
+                                                                                                   null_order, rank_percentage);
 
 template <typename Base>
 std::unique_ptr<Base> make_count_aggregation(null_policy null_handling)

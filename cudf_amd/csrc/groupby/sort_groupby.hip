@@ -8,7 +8,7 @@
 // Digits in which all words agree are skipped (one OR/AND reduction per word column tells), so a 32-bit key column of a few
 // million distinct values costs three passes, not eight. The kinds the hash engine serves are handed to it with the group label
 // as the key and come back aligned to the sorted unique keys.
-#include "call.hpp"
+#include "sort_helper.hpp"
 #include "../common/profiler.hpp"
 
 #include <cudf/copying.hpp>
@@ -41,30 +41,6 @@ constexpr int RS_WAVES   = RS_THREADS / 64;
 constexpr int RS_ITEMS   = 16;                     // keys per thread
 constexpr int RS_TILE    = RS_THREADS * RS_ITEMS;  // keys per workgroup
 
-// ---------------------------------------------------------------------------------------------------------
-// order-preserving 64-bit word of one element: unsigned comparison of words == the reference's ascending order of values
-// (NaN above every number and all NaNs one value, -0 == +0: cpp/include/cudf/detail/row_operator/lexicographic.cuh)
-__device__ __forceinline__ uint64_t sortable_word(device_column const& c, int64_t row)
-{
-  uint64_t const raw = col_load_bits(c, row);
-  switch (c.cls) {
-    case CLS_SINT: {
-      int const sh = 64 - 8 * c.width;
-      return static_cast<uint64_t>(static_cast<int64_t>(raw << sh) >> sh) ^ 0x8000000000000000ull;
-    }
-    case CLS_BOOL: return raw != 0;
-    case CLS_F32: {
-      uint32_t b = static_cast<uint32_t>(cudf::detail::normalize_key_bits(raw, CLS_F32));
-      return b ^ ((b >> 31) ? 0xffffffffu : 0x80000000u);
-    }
-    case CLS_F64: {
-      uint64_t b = cudf::detail::normalize_key_bits(raw, CLS_F64);
-      return b ^ ((b >> 63) ? 0xffffffffffffffffull : 0x8000000000000000ull);
-    }
-    default: return raw;
-  }
-}
-
 __device__ __forceinline__ uint64_t wave_or(uint64_t v)
 {
   for (int o = 32; o > 0; o >>= 1) v |= __shfl_xor(v, o, 64);
@@ -81,7 +57,7 @@ enum word_source : int32_t {
   WORD_VALUE      = 0,  // sortable_word(col[row]); 0 for a null
   WORD_NULL_FLAG  = 1,  // 1 for a null of col
   WORD_ANY_NULL   = 2,  // 1 if any column of the table holds a null in the row
-  WORD_LABEL_NULL = 3   // (label[payload] << 1) | null flag of col[row]
+  WORD_LABEL_NULL = 3   // (label[payload] << 1) | null flag of col[row] (nulls_first: valid flag)
 };
 
 struct fill_args {
@@ -95,6 +71,7 @@ struct fill_args {
   uint64_t* or_and;          // [0] |= word, [1] &= word
   uint32_t* ones;            // WORD_ANY_NULL: number of words equal to 1
   int32_t source;
+  bool nulls_first;          // WORD_LABEL_NULL: the flag is 1 for a valid row instead of a null one
 };
 
 __global__ void __launch_bounds__(256) k_fill_words(fill_args a)
@@ -113,7 +90,7 @@ __global__ void __launch_bounds__(256) k_fill_words(fill_args a)
       ones += static_cast<uint32_t>(w);
     } else {
       uint32_t const row = gload(a.order + p);
-      w = (static_cast<uint64_t>(static_cast<uint32_t>(gload(a.labels + p))) << 1) | (col_is_valid(a.col, row) ? 0 : 1);
+      w = (static_cast<uint64_t>(static_cast<uint32_t>(gload(a.labels + p))) << 1) | (col_is_valid(a.col, row) != a.nulls_first ? 0 : 1);
     }
     gstore(a.words + i, w);
     vor |= w;
@@ -132,13 +109,15 @@ __global__ void __launch_bounds__(256) k_fill_words(fill_args a)
 }
 
 // WORD_VALUE through order: word of values[order[payload]] (the second sort)
-__global__ void __launch_bounds__(256) k_fill_value_words(device_column col, uint32_t const* order, int64_t n, uint64_t* words,
-                                                          uint64_t* or_and)
+// (descending: the inverted word)
+__global__ void __launch_bounds__(256) k_fill_value_words(device_column col, uint32_t const* order, int64_t n, bool descending,
+                                                          uint64_t* words, uint64_t* or_and)
 {
   uint64_t vor = 0, vand = ~0ull;
   for (int64_t i = static_cast<int64_t>(blockIdx.x) * 256 + threadIdx.x; i < n; i += static_cast<int64_t>(gridDim.x) * 256) {
     uint32_t const row = gload(order + i);
-    uint64_t const w   = col_is_valid(col, row) ? sortable_word(col, row) : 0;
+    uint64_t w         = col_is_valid(col, row) ? sortable_word(col, row) : 0;
+    if (descending) w = ~w;
     gstore(words + i, w);
     vor |= w;
     vand &= w;
@@ -369,7 +348,8 @@ __global__ void __launch_bounds__(SC_THREADS) k_scan_apply(uint32_t const* in, u
   }
 }
 
-// out[0 .. n) = exclusive prefix sums of in[0 .. n); *total (device, optional) = the sum. in == out is allowed.
+}  // namespace
+
 void exclusive_scan(uint32_t const* in, uint32_t* out, int64_t n, uint32_t* total, scratch& sc, hipStream_t s)
 {
   if (n <= 0) {
@@ -385,6 +365,7 @@ void exclusive_scan(uint32_t const* in, uint32_t* out, int64_t n, uint32_t* tota
   CUDF_HIP_TRY(hipGetLastError());
 }
 
+namespace {
 // ---------------------------------------------------------------------------------------------------------
 // (word, payload) pairs in two buffers each; sort_by() runs the passes one word column needs
 class pair_sorter {
@@ -681,51 +662,67 @@ __global__ void __launch_bounds__(256) k_quantiles(quantile_args a)
 
 bool arithmetic(type_id t) { return t >= type_id::INT8 && t <= type_id::BOOL8; }
 
-unsigned blocks_of(int64_t n) { return static_cast<unsigned>(std::max<int64_t>((n + 255) / 256, 1)); }
-
 // The reference's sort_groupby_helper (cpp/include/cudf/detail/groupby/sort_helper.hpp): the key order, the group labels and offsets,
 // and per values column the order inside the groups.
-struct helper {
-  table_view keys;
-  device_table dkeys;
-  int64_t n{0};    // rows
-  int64_t nk{0};   // rows whose key takes part (n minus the rows of excluded null keys)
-  int32_t G{0};    // groups
-  uint32_t* order{nullptr};     // position in key order -> row, nk used
-  int32_t* labels{nullptr};     // per position
-  int32_t* offsets{nullptr};    // G + 1
-  int32_t* first_row{nullptr};  // per group: a row holding its key
-  scratch keep;                 // the arrays above
-  hipStream_t s;
+}  // namespace
 
-  helper(table_view const& k, hipStream_t stream) : keys{k}, dkeys{cudf::detail::make_device_table(k)}, keep{stream, get_current_device_resource_ref(), {}}, s{stream} {}
+helper::helper(table_view const& k, hipStream_t stream)
+  : keys{k}, dkeys{cudf::detail::make_device_table(k)}, keep{stream, get_current_device_resource_ref(), {}}, s{stream}
+{
+}
 
-  // inner_values: a values column whose order INSIDE the groups is wanted and nobody needs the rows of a group in their original
-  // order (no NTH_ELEMENT in the call): its words are sorted first, the key columns after them - one sort yields the groups AND that
-  // column's (key, null, value) order, instead of a key sort plus a second sort by (label, null, value): 11 instead of 14 passes and
-  // one gather instead of two at 100M rows on 1M groups.
-  void build(bool exclude_null_keys, bool presorted, column_view const* inner_values = nullptr)
-  {
-    n = keys.num_rows();
-    bool const keys_have_nulls = std::any_of(keys.begin(), keys.end(), [](auto const& c) { return c.has_nulls(); });
-    // pre-sorted keys with nulls to drop are sorted like any others (reference sort_helper.cu:51-54)
-    if (presorted && exclude_null_keys && keys_have_nulls) presorted = false;
-    order = keep.alloc<uint32_t>(static_cast<std::size_t>(n));
-    nk    = n;
-    scratch tmp{s, get_current_device_resource_ref(), {}};
-    auto* flags       = tmp.alloc<uint32_t>(static_cast<std::size_t>(n));
-    bool flags_filled = false;
-    if (presorted) {  // the rows as they lie: no sorter, no scratch for one
-      hipLaunchKernelGGL(k_iota, dim3(blocks_of(n)), dim3(256), 0, s, order, n);
-    } else {
-      scratch sort_tmp{s, get_current_device_resource_ref(), {}};
-      pair_sorter sorter{n, sort_tmp, s};
-      if (!presorted && inner_values != nullptr) {
+// inner_values: a values column whose order INSIDE the groups is wanted and nobody needs the rows of a group in their original
+// order (no NTH_ELEMENT in the call): its words are sorted first, the key columns after them - one sort yields the groups AND that
+// column's (key, null, value) order, instead of a key sort plus a second sort by (label, null, value): 11 instead of 14 passes and
+// one gather instead of two at 100M rows on 1M groups.
+void helper::build(bool exclude_null_keys, bool presorted, column_view const* inner_values)
+{
+  n = keys.num_rows();
+  bool const keys_have_nulls = std::any_of(keys.begin(), keys.end(), [](auto const& c) { return c.has_nulls(); });
+  // pre-sorted keys with nulls to drop are sorted like any others (reference sort_helper.cu:51-54)
+  if (presorted && exclude_null_keys && keys_have_nulls) presorted = false;
+  order = keep.alloc<uint32_t>(static_cast<std::size_t>(n));
+  nk    = n;
+  scratch tmp{s, get_current_device_resource_ref(), {}};
+  auto* flags       = tmp.alloc<uint32_t>(static_cast<std::size_t>(n));
+  bool flags_filled = false;
+  if (presorted) {  // the rows as they lie: no sorter, no scratch for one
+    hipLaunchKernelGGL(k_iota, dim3(blocks_of(n)), dim3(256), 0, s, order, n);
+    identity_order = true;
+  } else {
+    scratch sort_tmp{s, get_current_device_resource_ref(), {}};
+    pair_sorter sorter{n, sort_tmp, s};
+    if (!presorted && inner_values != nullptr) {
+      fill_args fa{};
+      fa.col    = cudf::detail::make_device_column(*inner_values);
+      fa.n      = n;
+      fa.or_and = sorter.or_and();
+      fa.source = WORD_VALUE;
+      sorter.reset_reduction();
+      fa.payload = sorter.payload();
+      fa.words   = sorter.words();
+      {
+        prof::scope p_{"sort_words", s};
+        hipLaunchKernelGGL(k_fill_words, dim3(fill_grid(n)), dim3(256), 0, s, fa);
+      }
+      sorter.sort_filled();
+      if (inner_values->has_nulls()) {  // nulls after the values
+        sorter.reset_reduction();
+        fa.source  = WORD_NULL_FLAG;
+        fa.payload = sorter.payload();
+        fa.words   = sorter.words();
+        hipLaunchKernelGGL(k_fill_words, dim3(fill_grid(n)), dim3(256), 0, s, fa);
+        sorter.sort_filled();
+      }
+      _value_orders_in_key_order = key_of(*inner_values, false, false);
+    }
+    if (!presorted) {
+      for (int c = dkeys.ncols - 1; c >= 0; --c) {
         fill_args fa{};
-        fa.col    = cudf::detail::make_device_column(*inner_values);
-        fa.n      = n;
-        fa.or_and = sorter.or_and();
-        fa.source = WORD_VALUE;
+        fa.col     = dkeys.col[c];
+        fa.n       = n;
+        fa.or_and  = sorter.or_and();
+        fa.source  = WORD_VALUE;
         sorter.reset_reduction();
         fa.payload = sorter.payload();
         fa.words   = sorter.words();
@@ -734,7 +731,7 @@ struct helper {
           hipLaunchKernelGGL(k_fill_words, dim3(fill_grid(n)), dim3(256), 0, s, fa);
         }
         sorter.sort_filled();
-        if (inner_values->has_nulls()) {  // nulls after the values
+        if (keys.column(c).has_nulls()) {  // nulls after the values of the column
           sorter.reset_reduction();
           fa.source  = WORD_NULL_FLAG;
           fa.payload = sorter.payload();
@@ -742,130 +739,104 @@ struct helper {
           hipLaunchKernelGGL(k_fill_words, dim3(fill_grid(n)), dim3(256), 0, s, fa);
           sorter.sort_filled();
         }
-        _value_orders_in_key_order = std::make_pair(inner_values->head(), inner_values->offset());
       }
-      if (!presorted) {
-        for (int c = dkeys.ncols - 1; c >= 0; --c) {
-          fill_args fa{};
-          fa.col     = dkeys.col[c];
-          fa.n       = n;
-          fa.or_and  = sorter.or_and();
-          fa.source  = WORD_VALUE;
-          sorter.reset_reduction();
-          fa.payload = sorter.payload();
-          fa.words   = sorter.words();
-          {
-            prof::scope p_{"sort_words", s};
-            hipLaunchKernelGGL(k_fill_words, dim3(fill_grid(n)), dim3(256), 0, s, fa);
-          }
-          sorter.sort_filled();
-          if (keys.column(c).has_nulls()) {  // nulls after the values of the column
-            sorter.reset_reduction();
-            fa.source  = WORD_NULL_FLAG;
-            fa.payload = sorter.payload();
-            fa.words   = sorter.words();
-            hipLaunchKernelGGL(k_fill_words, dim3(fill_grid(n)), dim3(256), 0, s, fa);
-            sorter.sort_filled();
-          }
-        }
-        if (exclude_null_keys && keys_have_nulls) {  // rows with a null in any key column to the back, then off the end
-          fill_args fa{};
-          fa.keys   = dkeys;
-          fa.n      = n;
-          fa.or_and = sorter.or_and();
-          fa.ones   = sorter.ones();
-          fa.source = WORD_ANY_NULL;
-          sorter.reset_reduction();
-          fa.payload = sorter.payload();
-          fa.words   = sorter.words();
-          hipLaunchKernelGGL(k_fill_words, dim3(fill_grid(n)), dim3(256), 0, s, fa);
-          nk = n - sorter.sort_filled();
-        }
+      if (exclude_null_keys && keys_have_nulls) {  // rows with a null in any key column to the back, then off the end
+        fill_args fa{};
+        fa.keys   = dkeys;
+        fa.n      = n;
+        fa.or_and = sorter.or_and();
+        fa.ones   = sorter.ones();
+        fa.source = WORD_ANY_NULL;
+        sorter.reset_reduction();
+        fa.payload = sorter.payload();
+        fa.words   = sorter.words();
+        hipLaunchKernelGGL(k_fill_words, dim3(fill_grid(n)), dim3(256), 0, s, fa);
+        nk = n - sorter.sort_filled();
       }
-      CUDF_HIP_TRY(hipMemcpyAsync(order, sorter.finish(), static_cast<std::size_t>(n) * sizeof(uint32_t), hipMemcpyDeviceToDevice, s));
-      if (!presorted && dkeys.ncols == 1 && !keys_have_nulls) {
-        prof::scope p_{"sort_boundaries", s};
-        hipLaunchKernelGGL(k_boundaries_of_words, dim3(blocks_of(n)), dim3(256), 0, s, sorter.words(), n, flags);
-        flags_filled = true;
-      }
-      CUDF_HIP_TRY(hipGetLastError());
     }
-    if (nk == 0) {
-      G = 0;
-      return;
-    }
-    labels       = keep.alloc<int32_t>(static_cast<std::size_t>(nk));
-    auto* before = tmp.alloc<uint32_t>(static_cast<std::size_t>(nk) + 1);
-    if (!flags_filled) {
+    CUDF_HIP_TRY(hipMemcpyAsync(order, sorter.finish(), static_cast<std::size_t>(n) * sizeof(uint32_t), hipMemcpyDeviceToDevice, s));
+    if (!presorted && dkeys.ncols == 1 && !keys_have_nulls) {
       prof::scope p_{"sort_boundaries", s};
-      hipLaunchKernelGGL(k_boundaries, dim3(blocks_of(nk)), dim3(256), 0, s, dkeys, order, nk, flags);
+      hipLaunchKernelGGL(k_boundaries_of_words, dim3(blocks_of(n)), dim3(256), 0, s, sorter.words(), n, flags);
+      flags_filled = true;
     }
-    exclusive_scan(flags, before, nk, before + nk, tmp, s);
-    uint32_t h_groups = 0;
-    CUDF_HIP_TRY(hipMemcpyAsync(&h_groups, before + nk, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
-    CUDF_HIP_TRY(hipStreamSynchronize(s));
-    G         = static_cast<int32_t>(h_groups);
-    offsets   = keep.alloc<int32_t>(static_cast<std::size_t>(G) + 1);
-    first_row = keep.alloc<int32_t>(static_cast<std::size_t>(G));
-    hipLaunchKernelGGL(k_labels, dim3(blocks_of(nk)), dim3(256), 0, s, flags, before, order, nk, labels, offsets, first_row);
-    hipLaunchKernelGGL(k_fill_i32, dim3(1), dim3(256), 0, s, offsets + G, 1, static_cast<int32_t>(nk));
     CUDF_HIP_TRY(hipGetLastError());
   }
+  if (nk == 0) {
+    G = 0;
+    return;
+  }
+  labels       = keep.alloc<int32_t>(static_cast<std::size_t>(nk));
+  auto* before = tmp.alloc<uint32_t>(static_cast<std::size_t>(nk) + 1);
+  if (!flags_filled) {
+    prof::scope p_{"sort_boundaries", s};
+    hipLaunchKernelGGL(k_boundaries, dim3(blocks_of(nk)), dim3(256), 0, s, dkeys, order, nk, flags);
+  }
+  exclusive_scan(flags, before, nk, before + nk, tmp, s);
+  uint32_t h_groups = 0;
+  CUDF_HIP_TRY(hipMemcpyAsync(&h_groups, before + nk, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+  CUDF_HIP_TRY(hipStreamSynchronize(s));
+  G         = static_cast<int32_t>(h_groups);
+  offsets   = keep.alloc<int32_t>(static_cast<std::size_t>(G) + 1);
+  first_row = keep.alloc<int32_t>(static_cast<std::size_t>(G));
+  hipLaunchKernelGGL(k_labels, dim3(blocks_of(nk)), dim3(256), 0, s, flags, before, order, nk, labels, offsets, first_row);
+  hipLaunchKernelGGL(k_fill_i32, dim3(1), dim3(256), 0, s, offsets + G, 1, static_cast<int32_t>(nk));
+  CUDF_HIP_TRY(hipGetLastError());
+}
 
-  // rows in (label, null, value) order (reference sort_helper.cu:205-225 sorted_values): vrow[i] for i in the group's range
-  uint32_t* value_order(column_view const& values)
+// rows in (label, null, value) order (reference sort_helper.cu:205-225 sorted_values): vrow[i] for i in the group's range
+uint32_t* helper::value_order(column_view const& values, bool descending, bool nulls_first)
+{
+  auto const key = key_of(values, descending, nulls_first);
+  if (_value_orders_in_key_order == key) return order;  // (build() sorted this column's words before the keys)
+  if (auto it = _value_orders.find(key); it != _value_orders.end()) return it->second;
+  auto* vrow = keep.alloc<uint32_t>(static_cast<std::size_t>(nk));
   {
-    auto const key = std::make_pair(values.head(), values.offset());
-    if (_value_orders_in_key_order == key) return order;  // (build() sorted this column's words before the keys)
-    if (auto it = _value_orders.find(key); it != _value_orders.end()) return it->second;
-    auto* vrow = keep.alloc<uint32_t>(static_cast<std::size_t>(nk));
+    auto const col = cudf::detail::make_device_column(values);
+    scratch tmp{s, get_current_device_resource_ref(), {}};
+    pair_sorter sorter{nk, tmp, s};
+    sorter.reset_reduction();
     {
-      auto const col = cudf::detail::make_device_column(values);
-      scratch tmp{s, get_current_device_resource_ref(), {}};
-      pair_sorter sorter{nk, tmp, s};
-      sorter.reset_reduction();
-      {
-        prof::scope p_{"sort_words", s};
-        hipLaunchKernelGGL(k_fill_value_words, dim3(fill_grid(nk)), dim3(256), 0, s, col, order, nk, sorter.words(), sorter.or_and());
-      }
-      sorter.sort_filled();
-      fill_args fa{};
-      fa.col     = col;
-      fa.order   = order;
-      fa.labels  = labels;
-      fa.n       = nk;
-      fa.or_and  = sorter.or_and();
-      fa.source  = WORD_LABEL_NULL;
-      sorter.reset_reduction();
-      fa.payload = sorter.payload();
-      fa.words   = sorter.words();
-      {
-        prof::scope p_{"sort_words", s};
-        hipLaunchKernelGGL(k_fill_words, dim3(fill_grid(nk)), dim3(256), 0, s, fa);
-      }
-      sorter.sort_filled();
-      hipLaunchKernelGGL(k_compose, dim3(blocks_of(nk)), dim3(256), 0, s, order, sorter.finish(), nk, vrow);
-      CUDF_HIP_TRY(hipGetLastError());
+      prof::scope p_{"sort_words", s};
+      hipLaunchKernelGGL(k_fill_value_words, dim3(fill_grid(nk)), dim3(256), 0, s, col, order, nk, descending, sorter.words(),
+                         sorter.or_and());
     }
-    _value_orders.emplace(key, vrow);
-    return vrow;
+    sorter.sort_filled();
+    fill_args fa{};
+    fa.col     = col;
+    fa.order   = order;
+    fa.labels  = labels;
+    fa.n       = nk;
+    fa.or_and  = sorter.or_and();
+    fa.source  = WORD_LABEL_NULL;
+    fa.nulls_first = nulls_first;
+    sorter.reset_reduction();
+    fa.payload = sorter.payload();
+    fa.words   = sorter.words();
+    {
+      prof::scope p_{"sort_words", s};
+      hipLaunchKernelGGL(k_fill_words, dim3(fill_grid(nk)), dim3(256), 0, s, fa);
+    }
+    sorter.sort_filled();
+    hipLaunchKernelGGL(k_compose, dim3(blocks_of(nk)), dim3(256), 0, s, order, sorter.finish(), nk, vrow);
+    CUDF_HIP_TRY(hipGetLastError());
   }
+  _value_orders.emplace(key, vrow);
+  return vrow;
+}
 
-  // valid rows of `values` before each position of the key order (nk + 1 entries), and per group
-  uint32_t* valid_before(column_view const& values, scratch& tmp, uint32_t** flags_out = nullptr)
-  {
-    auto* flags  = tmp.alloc<uint32_t>(static_cast<std::size_t>(nk));
-    auto* before = tmp.alloc<uint32_t>(static_cast<std::size_t>(nk) + 1);
-    hipLaunchKernelGGL(k_valid_flags, dim3(blocks_of(nk)), dim3(256), 0, s, cudf::detail::make_device_column(values), order, nk, flags);
-    exclusive_scan(flags, before, nk, before + nk, tmp, s);
-    if (flags_out) *flags_out = flags;
-    return before;
-  }
+// valid rows of `values` before each position of the key order (nk + 1 entries), and per group
+uint32_t* helper::valid_before(column_view const& values, scratch& tmp, uint32_t** flags_out)
+{
+  auto* flags  = tmp.alloc<uint32_t>(static_cast<std::size_t>(nk));
+  auto* before = tmp.alloc<uint32_t>(static_cast<std::size_t>(nk) + 1);
+  hipLaunchKernelGGL(k_valid_flags, dim3(blocks_of(nk)), dim3(256), 0, s, cudf::detail::make_device_column(values), order, nk, flags);
+  exclusive_scan(flags, before, nk, before + nk, tmp, s);
+  if (flags_out) *flags_out = flags;
+  return before;
+}
 
- private:
-  std::map<std::pair<void const*, size_type>, uint32_t*> _value_orders;
-  std::pair<void const*, size_type> _value_orders_in_key_order{nullptr, 0};
-};
+namespace {
 
 std::unique_ptr<column> int32_column(int64_t size, stream_ref stream, rmm::device_async_resource_ref mr)
 {

@@ -3,7 +3,8 @@
 // (cpp/include/cudf/aggregation.hpp:78-121) because pylibcudf passes them through as ints; factories
 // mirror :212-367. Constructible on this path: the hash-groupby kinds (SUM, SUM_OVERFLOW, PRODUCT, MIN, MAX,
 // COUNT_VALID, COUNT_ALL, SUM_OF_SQUARES, MEAN, M2, VARIANCE, STD, ARGMAX, ARGMIN) and the sort-groupby kinds
-// MEDIAN, QUANTILE, NUNIQUE, NTH_ELEMENT; the rest of the enum is kept so that values line up.
+// MEDIAN, QUANTILE, NUNIQUE, NTH_ELEMENT; for groupby::scan, SUM, PRODUCT, MIN, MAX, COUNT_VALID, COUNT_ALL and RANK; the rest of
+// the enum is kept so that values line up.
 #pragma once
 #include <cudf/types.hpp>
 #include <cudf/utilities/error.hpp>
@@ -12,6 +13,21 @@
 #include <vector>
 
 namespace cudf {
+
+// How a RANK scan breaks ties (reference aggregation.hpp:37-43)
+enum class rank_method : int32_t {
+  FIRST,    // stable order: ties by input order
+  AVERAGE,  // mean of the tied rows' FIRST ranks
+  MIN,      // lowest FIRST rank of the tied rows
+  MAX,      // highest FIRST rank of the tied rows
+  DENSE     // 1 + the number of distinct values before
+};
+// Whether and how a RANK scan is normalised (reference aggregation.hpp:50-54)
+enum class rank_percentage : int32_t {
+  NONE,             // the rank
+  ZERO_NORMALIZED,  // rank / count
+  ONE_NORMALIZED    // (rank - 1) / (count - 1)
+};
 
 class aggregation {
  public:
@@ -72,6 +88,8 @@ class aggregation {
 
 class groupby_aggregation : public virtual aggregation {};
 class reduce_aggregation : public virtual aggregation {};
+// Kinds a groupby scan accepts: SUM, PRODUCT, MIN, MAX, COUNT_VALID, COUNT_ALL and RANK (reference aggregation.hpp:132-143)
+class groupby_scan_aggregation : public virtual aggregation {};
 
 template <typename Base = aggregation> std::unique_ptr<Base> make_sum_aggregation();
 // SUM with overflow detection: struct {sum: source type, overflow: bool} (reference aggregation.hpp:214-217)
@@ -98,6 +116,14 @@ std::unique_ptr<Base> make_quantile_aggregation(std::vector<double> const& quant
                                                 interpolation interp = interpolation::LINEAR);
 template <typename Base = aggregation>
 std::unique_ptr<Base> make_nunique_aggregation(null_policy null_handling = null_policy::EXCLUDE);
+// RANK, a scan kind only (reference aggregation.hpp:483-487). Ranks run over the group's rows in (value, null_precedence) order
+// by column_order; EXCLUDE masks the ranks of null rows, which still take their places in that order.
+template <typename Base = aggregation>
+std::unique_ptr<Base> make_rank_aggregation(rank_method method,
+                                            order column_order         = order::ASCENDING,
+                                            null_policy null_handling  = null_policy::EXCLUDE,
+                                            null_order null_precedence = null_order::AFTER,
+                                            rank_percentage percentage = rank_percentage::NONE);
 
 namespace detail {
 // Accumulator/result type of `k` applied to a column of type `source`

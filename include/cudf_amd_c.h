@@ -116,6 +116,24 @@ cudf_amd_status cudf_amd_groupby_aggregate(const cudf_amd_column_view* keys, int
                                            void* stream, cudf_amd_table_t* out_keys, cudf_amd_table_t* out_results,
                                            int32_t* out_path);
 
+/* ---- cudf::groupby::groupby(keys, null_handling, keys_are_sorted).scan(requests, stream, mr)
+ * (reference cpp/include/cudf/groupby.hpp:186-247). Kinds: SUM, PRODUCT, MIN, MAX, COUNT_VALID, COUNT_ALL, RANK; any other kind
+ * fails with CUDF_AMD_LOGIC_ERROR. RANK: params[k] = cudf::rank_method (0 FIRST, 1 AVERAGE, 2 MIN, 3 MAX, 4 DENSE; default FIRST),
+ * params2[k] = column_order + 2 * null_precedence + 4 * null_handling + 8 * percentage (cudf::order, cudf::null_order,
+ * cudf::null_policy, cudf::rank_percentage values; NULL or 0 = ASCENDING, AFTER, EXCLUDE, NONE). out_keys: the keys of the rows
+ * that take part, in group order; out_results: one column per aggregation, flattened in request order, rows aligned to out_keys. */
+cudf_amd_status cudf_amd_groupby_scan(const cudf_amd_column_view* keys, int32_t num_keys, int32_t include_null_keys,
+                                      int32_t keys_are_sorted, const cudf_amd_aggregation_request* requests, int32_t num_requests,
+                                      void* stream, cudf_amd_table_t* out_keys, cudf_amd_table_t* out_results);
+
+/* ---- cudf::groupby::groupby(keys, null_handling, keys_are_sorted).replace_nulls(values, policies, stream, mr)
+ * (reference cpp/include/cudf/groupby.hpp:332-371). policies[i]: 0 = replace_policy::PRECEDING, 1 = FOLLOWING, one per values
+ * column. out_keys / out_values in group order, as cudf_amd_groupby_scan. */
+cudf_amd_status cudf_amd_groupby_replace_nulls(const cudf_amd_column_view* keys, int32_t num_keys, int32_t include_null_keys,
+                                               int32_t keys_are_sorted, const cudf_amd_column_view* values, int32_t num_values,
+                                               const int32_t* policies, void* stream, cudf_amd_table_t* out_keys,
+                                               cudf_amd_table_t* out_values);
+
 /* ---- cudf::inner_join / left_join / full_join(left_keys, right_keys, compare_nulls, stream, mr)
  * (reference cpp/include/cudf/join/join.hpp:160-166 and the left/full overloads; src/join/join.cu:30-118).
  * nulls_equal: 1 = null_equality::EQUAL, 0 = UNEQUAL. kind: 0 inner, 1 left, 2 full.
