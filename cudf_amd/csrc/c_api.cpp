@@ -10,6 +10,7 @@
 #include <cudf/groupby.hpp>
 #include <cudf/partitioning.hpp>
 #include <cudf/interop.hpp>
+#include <cudf/join/filtered_join.hpp>
 #include <cudf/join/hash_join.hpp>
 #include <cudf/join/join.hpp>
 #include <cudf/table/table.hpp>
@@ -32,6 +33,9 @@ struct cudf_amd_comm_s {
 };
 struct cudf_amd_hash_join_s {
   std::unique_ptr<cudf::hash_join> hj;
+};
+struct cudf_amd_filtered_join_s {
+  std::unique_ptr<cudf::filtered_join> fj;
 };
 
 namespace {
@@ -493,6 +497,38 @@ cudf_amd_status cudf_amd_hash_join_finalize_full(const int32_t* const* left_part
     }
     cudf::stream_ref const s{as_stream(stream)};
     *out_indices = indices_to_table(cudf::hash_join::finalize_partitioned_full_join(lp, rp, left_num_rows, right_num_rows, s));
+  });
+}
+
+cudf_amd_status cudf_amd_filtered_join_create(const cudf_amd_column_view* right_keys, int32_t num_right, int32_t nulls_equal,
+                                              double load_factor, void* stream, cudf_amd_filtered_join_t* out)
+{
+  return guarded([&] {
+    *out          = nullptr;
+    auto const r  = to_table(right_keys, num_right);
+    auto const eq = nulls_equal ? cudf::null_equality::EQUAL : cudf::null_equality::UNEQUAL;
+    cudf::stream_ref const s{as_stream(stream)};
+    auto h = std::make_unique<cudf_amd_filtered_join_s>();
+    if (load_factor < 0) h->fj = std::make_unique<cudf::filtered_join>(r, eq, s);
+    else h->fj = std::make_unique<cudf::filtered_join>(r, eq, load_factor, s);
+    *out = h.release();
+  });
+}
+void cudf_amd_filtered_join_destroy(cudf_amd_filtered_join_t h) { delete h; }
+
+cudf_amd_status cudf_amd_filtered_join_probe(cudf_amd_filtered_join_t h, const cudf_amd_column_view* left_keys, int32_t num_left,
+                                             int32_t kind, void* stream, cudf_amd_table_t* out_indices)
+{
+  return guarded([&] {
+    *out_indices = nullptr;
+    CUDF_EXPECTS(h != nullptr && h->fj != nullptr, "null filtered_join handle", std::invalid_argument);
+    CUDF_EXPECTS(kind == 0 || kind == 1, "filtered join kind must be 0 (semi) or 1 (anti)", std::invalid_argument);
+    auto const l = to_table(left_keys, num_left);
+    cudf::stream_ref const s{as_stream(stream)};
+    auto idx = kind == 0 ? h->fj->semi_join(l, s) : h->fj->anti_join(l, s);
+    auto t   = std::make_unique<cudf_amd_table_s>();
+    t->cols.push_back(std::make_unique<cudf::column>(std::move(*idx), rmm::device_buffer{}, 0));
+    *out_indices = t.release();
   });
 }
 

@@ -1,0 +1,389 @@
+// SPDX-License-Identifier: Apache-2.0
+// gfx950 kernels of cudf::filtered_join (filtered_join_impl.hpp): the bitmap and hash-set builds, the probes that answer one bit per
+// left row, and the ordered compaction of those bits into ascending row indices. Replaces the reference's cuco::static_set
+// insert / contains and thrust::copy_if over a counting iterator (cpp/src/join/filtered_join/filtered_join.cu, semi_anti_join).
+#include "filtered_join_impl.hpp"
+#include "../common/profiler.hpp"
+
+#include <cudf/utilities/error.hpp>
+
+#include <algorithm>
+#include <mutex>
+
+namespace cudf::detail::fjoin {
+namespace {
+
+constexpr int PROBE_THREADS = 256;   // pass 1 (global bitmap, set) and pass 2: 4 waves per workgroup
+constexpr int LDS_THREADS   = 1024;  // pass 1 from an LDS bitmap: 16 waves share one copy
+constexpr int LDS_BYTES_MAX = 128 * 1024;
+
+// element i of an integer column widened to 64 bits: sign-extended (SIGNED) or zero-extended
+template <int W, bool SIGNED>
+__device__ __forceinline__ uint64_t load_int(device_column const& c, int64_t i)
+{
+  int64_t const e = static_cast<int64_t>(c.offset) + i;
+  if constexpr (W == 1) {
+    uint8_t const v = gload(static_cast<uint8_t const*>(c.head) + e);
+    return SIGNED ? static_cast<uint64_t>(static_cast<int64_t>(static_cast<int8_t>(v))) : v;
+  } else if constexpr (W == 2) {
+    uint16_t const v = gload(static_cast<uint16_t const*>(c.head) + e);
+    return SIGNED ? static_cast<uint64_t>(static_cast<int64_t>(static_cast<int16_t>(v))) : v;
+  } else if constexpr (W == 4) {
+    uint32_t const v = gload(static_cast<uint32_t const*>(c.head) + e);
+    return SIGNED ? static_cast<uint64_t>(static_cast<int64_t>(static_cast<int32_t>(v))) : v;
+  } else {
+    return gload(static_cast<uint64_t const*>(c.head) + e);
+  }
+}
+
+// element i of a 4- or 8-byte column as raw bits, zero-extended
+template <int W>
+__device__ __forceinline__ uint64_t load_bits(device_column const& c, int64_t i)
+{
+  int64_t const e = static_cast<int64_t>(c.offset) + i;
+  if constexpr (W == 4) return gload(static_cast<uint32_t const*>(c.head) + e);
+  else return gload(static_cast<uint64_t const*>(c.head) + e);
+}
+
+// first slot of a row hash's probe sequence; 64-bit, so capacities beyond 2^32 slots are addressed
+__device__ __forceinline__ uint64_t home_slot(uint32_t h, uint64_t capacity) { return __umul64hi(mix64(h), capacity); }
+__device__ __forceinline__ uint64_t next_slot(uint64_t s, uint64_t capacity) { return s + 1 == capacity ? 0 : s + 1; }
+
+// ------------------------------------------------------------------ builds
+template <int W, bool SIGNED>
+__global__ void __launch_bounds__(256) k_bitmap_build(bitmap_args a)
+{
+  int64_t const stride = static_cast<int64_t>(gridDim.x) * blockDim.x;
+  bool seen_null       = false;
+  for (int64_t i = blockIdx.x * static_cast<int64_t>(blockDim.x) + threadIdx.x; i < a.nrows; i += stride) {
+    if (!col_is_valid(a.key, i)) {  // never inserted: a NULL probe key asks probe_args::null_match instead
+      seen_null = true;
+      continue;
+    }
+    uint64_t const off = load_int<W, SIGNED>(a.key, i) - a.lo;  // < range: lo and range cover every valid build key
+    if (off < a.range) atomicOr(a.bits + (off >> 5), 1u << (off & 31));
+  }
+  if (__any(seen_null) && (threadIdx.x & 63) == 0) gstore(a.seen_null, 1);
+}
+
+template <int W>
+__global__ void __launch_bounds__(256) k_set_build_inline(set_args a)
+{
+  device_column const& c = a.build.col[0];
+  int64_t const n        = a.build.nrows;
+  int64_t const stride   = static_cast<int64_t>(gridDim.x) * blockDim.x;
+  bool seen_null = false, seen_sentinel = false;
+  for (int64_t i = blockIdx.x * static_cast<int64_t>(blockDim.x) + threadIdx.x; i < n; i += stride) {
+    if (!col_is_valid(c, i)) {
+      seen_null = true;
+      continue;
+    }
+    uint64_t const key = normalize_key_bits(load_bits<W>(c, i), c.cls);
+    if (key == SET_EMPTY) {  // (8-byte keys only) the one value a slot cannot hold
+      seen_sentinel = true;
+      continue;
+    }
+    uint64_t s = home_slot(murmur3_32_bits(key, W, 0), a.capacity);
+    while (true) {
+      uint64_t cur = gload(a.slots + s);
+      if (cur == SET_EMPTY) {
+        cur = atomicCAS(reinterpret_cast<unsigned long long*>(a.slots + s), static_cast<unsigned long long>(SET_EMPTY),
+                        static_cast<unsigned long long>(key));
+        if (cur == SET_EMPTY) break;  // inserted
+      }
+      if (cur == key) break;  // a slot changes once, from empty to its key: an equal key is already in the set
+      s = next_slot(s, a.capacity);
+    }
+  }
+  if (__any(seen_null) && (threadIdx.x & 63) == 0) gstore(a.seen_null, 1);
+  if (__any(seen_sentinel) && (threadIdx.x & 63) == 0) gstore(a.seen_sentinel, 1);
+}
+
+__global__ void __launch_bounds__(256) k_set_build_rows(set_args a)
+{
+  int64_t const n      = a.build.nrows;
+  int64_t const stride = static_cast<int64_t>(gridDim.x) * blockDim.x;
+  bool const eq        = a.nulls_equal != 0;
+  for (int64_t i = blockIdx.x * static_cast<int64_t>(blockDim.x) + threadIdx.x; i < n; i += stride) {
+    if (!eq && row_has_null(a.build, i)) continue;  // null_equality::UNEQUAL: such a row equals no row
+    uint32_t const h     = row_hash(a.build, i, 0);
+    uint64_t const entry = (static_cast<uint64_t>(h) << 32) | static_cast<uint32_t>(i);
+    uint64_t s           = home_slot(h, a.capacity);
+    while (true) {
+      uint64_t cur = gload(a.slots + s);
+      if (cur == SET_EMPTY) {
+        cur = atomicCAS(reinterpret_cast<unsigned long long*>(a.slots + s), static_cast<unsigned long long>(SET_EMPTY),
+                        static_cast<unsigned long long>(entry));
+        if (cur == SET_EMPTY) break;
+      }
+      if ((cur >> 32) == h && rows_equal(a.build, static_cast<uint32_t>(cur), a.build, i, eq)) break;  // a distinct set
+      s = next_slot(s, a.capacity);
+    }
+  }
+}
+
+// ------------------------------------------------------------------ pass 1: one bit per left row
+// Wave `wave` tests rows [wave * chunk, + chunk) of the left table, UNROLL x 64 rows at a time: every lane first loads its rows'
+// keys (clamped to the chunk, so that the loads need no branch and stay in flight together), then tests them. The ballot of a
+// 64-row group is its mask word.
+template <int UNROLL, typename Probe>
+__device__ __forceinline__ void probe_chunk(probe_args const& a, int64_t wave, Probe const& p)
+{
+  using key_t          = typename Probe::key_t;
+  int const lane       = threadIdx.x & 63;
+  int64_t const begin  = wave * a.chunk;
+  int64_t const end    = a.nrows < begin + a.chunk ? a.nrows : begin + a.chunk;
+  bool const anti      = a.anti != 0;
+  unsigned long long n = 0;
+  for (int64_t r0 = begin; r0 < end; r0 += UNROLL * 64) {
+    key_t k[UNROLL];
+#pragma unroll
+    for (int j = 0; j < UNROLL; ++j) {
+      int64_t const r = r0 + j * 64 + lane;
+      k[j]            = p.load(r < end ? r : end - 1);
+    }
+#pragma unroll
+    for (int j = 0; j < UNROLL; ++j) {
+      int64_t const r = r0 + j * 64 + lane;
+      bool const q    = r < end && (p.test(k[j], r) != anti);
+      uint64_t const m = __ballot(q);
+      if (r0 + j * 64 < end) {
+        if (lane == 0) gstore(a.mask + ((r0 + j * 64) >> 6), m);
+        n += __popcll(m);
+      }
+    }
+  }
+  if (lane == 0 && wave < a.nwaves) gstore(a.counts + wave, n);
+}
+
+struct int_key {
+  uint64_t v;
+  bool valid;
+};
+
+template <int W, bool SIGNED, bool LDS>
+struct bitmap_probe {
+  using key_t = int_key;
+  probe_args const& a;
+  uint32_t const* lds;
+  __device__ int_key load(int64_t r) const
+  {
+    return {load_int<W, SIGNED>(a.probe.col[0], r), col_is_valid(a.probe.col[0], r)};
+  }
+  __device__ bool test(int_key k, int64_t) const
+  {
+    if (!k.valid) return a.null_match != 0;
+    uint64_t const off = k.v - a.bm.lo;
+    if (off >= a.bm.range) return false;  // outside the build keys' range: no memory access
+    uint32_t const word = LDS ? lds[off >> 5] : gload(a.bm.bits + (off >> 5));
+    return (word >> (off & 31)) & 1u;
+  }
+};
+
+template <int W, bool SIGNED>
+__global__ void __launch_bounds__(PROBE_THREADS) k_bitmap_probe(probe_args a)
+{
+  int64_t const wave = static_cast<int64_t>(blockIdx.x) * (PROBE_THREADS / 64) + (threadIdx.x >> 6);
+  probe_chunk<8>(a, wave, bitmap_probe<W, SIGNED, false>{a, nullptr});
+}
+
+template <int W, bool SIGNED>
+__global__ void __launch_bounds__(LDS_THREADS) k_bitmap_probe_lds(probe_args a)
+{
+  extern __shared__ __attribute__((aligned(16))) uint32_t s_bits[];
+  // the bitmap's words, 16 bytes at a time (the buffer and the LDS copy are whole 16-byte units)
+  int64_t const units = static_cast<int64_t>((a.bm.range + 127) >> 7);
+  for (int64_t u = threadIdx.x; u < units; u += LDS_THREADS)
+    reinterpret_cast<u32x4*>(s_bits)[u] = gload(reinterpret_cast<u32x4 const*>(a.bm.bits) + u);
+  __syncthreads();
+  int64_t const wave = static_cast<int64_t>(blockIdx.x) * (LDS_THREADS / 64) + (threadIdx.x >> 6);
+  probe_chunk<8>(a, wave, bitmap_probe<W, SIGNED, true>{a, s_bits});
+}
+
+template <int W>
+struct set_probe_inline {
+  using key_t = int_key;
+  probe_args const& a;
+  __device__ int_key load(int64_t r) const
+  {
+    device_column const& c = a.probe.col[0];
+    return {normalize_key_bits(load_bits<W>(c, r), c.cls), col_is_valid(c, r)};
+  }
+  __device__ bool test(int_key k, int64_t) const
+  {
+    if (!k.valid) return a.null_match != 0;
+    if (k.v == SET_EMPTY) return a.sentinel_match != 0;
+    uint64_t s = home_slot(murmur3_32_bits(k.v, W, 0), a.set.capacity);
+    while (true) {
+      uint64_t const cur = gload(a.set.slots + s);
+      if (cur == k.v) return true;
+      if (cur == SET_EMPTY) return false;
+      s = next_slot(s, a.set.capacity);
+    }
+  }
+};
+
+struct set_probe_rows {
+  struct key_t {};
+  probe_args const& a;
+  __device__ key_t load(int64_t) const { return {}; }
+  __device__ bool test(key_t, int64_t r) const
+  {
+    bool const eq = a.set.nulls_equal != 0;
+    if (!eq && row_has_null(a.probe, r)) return false;
+    uint32_t const h = row_hash(a.probe, r, 0);
+    uint64_t s       = home_slot(h, a.set.capacity);
+    while (true) {
+      uint64_t const cur = gload(a.set.slots + s);
+      if (cur == SET_EMPTY) return false;
+      if ((cur >> 32) == h && rows_equal(a.probe, r, a.set.build, static_cast<uint32_t>(cur), eq)) return true;
+      s = next_slot(s, a.set.capacity);
+    }
+  }
+};
+
+template <int W>
+__global__ void __launch_bounds__(PROBE_THREADS) k_set_probe_inline(probe_args a)
+{
+  int64_t const wave = static_cast<int64_t>(blockIdx.x) * (PROBE_THREADS / 64) + (threadIdx.x >> 6);
+  probe_chunk<4>(a, wave, set_probe_inline<W>{a});
+}
+
+__global__ void __launch_bounds__(PROBE_THREADS) k_set_probe_rows(probe_args a)
+{
+  int64_t const wave = static_cast<int64_t>(blockIdx.x) * (PROBE_THREADS / 64) + (threadIdx.x >> 6);
+  probe_chunk<1>(a, wave, set_probe_rows{a});
+}
+
+// ------------------------------------------------------------------ pass 2: ordered compaction
+// Wave `wave` streams the mask words of its chunk, 64 at a time (one per lane), and writes the rows of the set bits at its chunk's
+// offset (counts, scanned) plus the bits before them: the words' exclusive prefix over the wave, then each word's bits below the
+// lane (mbcnt). No atomics; the output is in row order.
+__global__ void __launch_bounds__(PROBE_THREADS) k_compact(probe_args a)
+{
+  int const lane      = threadIdx.x & 63;
+  int64_t const wave  = static_cast<int64_t>(blockIdx.x) * (PROBE_THREADS / 64) + (threadIdx.x >> 6);
+  int64_t const begin = wave * a.chunk;
+  int64_t const end   = a.nrows < begin + a.chunk ? a.nrows : begin + a.chunk;
+  if (begin >= end) return;
+  uint64_t base      = gload(a.counts + wave);
+  int64_t const w_end = (end + 63) >> 6;
+  for (int64_t w0 = begin >> 6; w0 < w_end; w0 += 64) {
+    uint64_t const word = w0 + lane < w_end ? gload(a.mask + w0 + lane) : 0;
+    uint32_t const c    = __popcll(word);
+    uint32_t inc        = c;
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+      uint32_t const t = __shfl_up(inc, o);
+      if (lane >= o) inc += t;
+    }
+    uint32_t const exc   = inc - c;
+    uint32_t const total = __shfl(inc, 63);
+    int const nw         = static_cast<int>(w_end - w0 < 64 ? w_end - w0 : 64);
+    for (int k = 0; k < nw; ++k) {
+      uint64_t const wk = __shfl(word, k);
+      if (wk == 0) continue;  // (uniform)
+      uint32_t const at   = __shfl(exc, k);
+      uint32_t const rank = __builtin_amdgcn_mbcnt_hi(static_cast<uint32_t>(wk >> 32), __builtin_amdgcn_mbcnt_lo(static_cast<uint32_t>(wk), 0u));
+      uint64_t const o    = base + at + rank;
+      if (((wk >> lane) & 1) && o < a.out_capacity) gstore(a.out + o, static_cast<size_type>((w0 + k) * 64 + lane));
+    }
+    base += total;
+  }
+}
+
+// an empty right table: anti_join returns every left row
+__global__ void __launch_bounds__(256) k_sequence(size_type* out, int64_t n)
+{
+  for (int64_t i = blockIdx.x * static_cast<int64_t>(blockDim.x) + threadIdx.x; i < n; i += static_cast<int64_t>(gridDim.x) * blockDim.x)
+    gstore(out + i, static_cast<size_type>(i));
+}
+
+unsigned grid_for(int64_t n)
+{
+  int64_t const blocks = (n + 255) / 256;
+  return static_cast<unsigned>(std::max<int64_t>(1, std::min<int64_t>(blocks, 256 * 16)));
+}
+
+template <typename F>
+void dispatch_int(int width, bool is_signed, F&& f)
+{
+  switch (width) {
+    case 1: return is_signed ? f.template operator()<1, true>() : f.template operator()<1, false>();
+    case 2: return is_signed ? f.template operator()<2, true>() : f.template operator()<2, false>();
+    case 4: return is_signed ? f.template operator()<4, true>() : f.template operator()<4, false>();
+    case 8: return is_signed ? f.template operator()<8, true>() : f.template operator()<8, false>();
+    default: CUDF_FAIL("filtered_join: the bitmap takes 1-, 2-, 4- or 8-byte integer keys");
+  }
+}
+}  // namespace
+
+uint64_t lds_bits_max() { return uint64_t{LDS_BYTES_MAX} * 8; }
+
+void launch_bitmap_build(bitmap_args const& a, hipStream_t stream)
+{
+  cudf::detail::prof::scope prof_{"fjoin_bitmap_build", stream};
+  dispatch_int(a.key.width, a.key.cls == CLS_SINT, [&]<int W, bool S>() {
+    hipLaunchKernelGGL((k_bitmap_build<W, S>), dim3(grid_for(a.nrows)), dim3(256), 0, stream, a);
+  });
+  CUDF_HIP_TRY(hipGetLastError());
+}
+
+void launch_set_build(set_args const& a, hipStream_t stream)
+{
+  cudf::detail::prof::scope prof_{"fjoin_set_build", stream};
+  unsigned const grid = grid_for(a.build.nrows);
+  if (!a.inline_key) hipLaunchKernelGGL(k_set_build_rows, dim3(grid), dim3(256), 0, stream, a);
+  else if (a.build.col[0].width == 4) hipLaunchKernelGGL(k_set_build_inline<4>, dim3(grid), dim3(256), 0, stream, a);
+  else hipLaunchKernelGGL(k_set_build_inline<8>, dim3(grid), dim3(256), 0, stream, a);
+  CUDF_HIP_TRY(hipGetLastError());
+}
+
+void launch_bitmap_probe(probe_args const& a, bool lds, hipStream_t stream)
+{
+  if (lds) {
+    CUDF_EXPECTS(a.bm.range <= lds_bits_max() && a.nwaves % (LDS_THREADS / 64) == 0, "filtered_join: bitmap exceeds the LDS probe");
+    std::size_t const bytes = static_cast<std::size_t>((a.bm.range + 127) >> 7) * 16;
+    cudf::detail::prof::scope prof_{"fjoin_probe_lds", stream};
+    dispatch_int(a.probe.col[0].width, a.probe.col[0].cls == CLS_SINT, [&]<int W, bool S>() {
+      static std::once_flag once;  // opt the kernel into more than 64 KiB of dynamic LDS, once per process
+      std::call_once(once, [] {
+        CUDF_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<void const*>(&k_bitmap_probe_lds<W, S>),
+                                         hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES_MAX));
+      });
+      hipLaunchKernelGGL((k_bitmap_probe_lds<W, S>), dim3(a.nwaves / (LDS_THREADS / 64)), dim3(LDS_THREADS), bytes, stream, a);
+    });
+  } else {
+    cudf::detail::prof::scope prof_{"fjoin_probe_bitmap", stream};
+    dispatch_int(a.probe.col[0].width, a.probe.col[0].cls == CLS_SINT, [&]<int W, bool S>() {
+      hipLaunchKernelGGL((k_bitmap_probe<W, S>), dim3(a.nwaves / (PROBE_THREADS / 64)), dim3(PROBE_THREADS), 0, stream, a);
+    });
+  }
+  CUDF_HIP_TRY(hipGetLastError());
+}
+
+void launch_set_probe(probe_args const& a, hipStream_t stream)
+{
+  cudf::detail::prof::scope prof_{"fjoin_probe_set", stream};
+  dim3 const grid(a.nwaves / (PROBE_THREADS / 64));
+  if (!a.set.inline_key) hipLaunchKernelGGL(k_set_probe_rows, grid, dim3(PROBE_THREADS), 0, stream, a);
+  else if (a.probe.col[0].width == 4) hipLaunchKernelGGL(k_set_probe_inline<4>, grid, dim3(PROBE_THREADS), 0, stream, a);
+  else hipLaunchKernelGGL(k_set_probe_inline<8>, grid, dim3(PROBE_THREADS), 0, stream, a);
+  CUDF_HIP_TRY(hipGetLastError());
+}
+
+void launch_fjoin_compact(probe_args const& a, hipStream_t stream)
+{
+  cudf::detail::prof::scope prof_{"fjoin_compact", stream};
+  hipLaunchKernelGGL(k_compact, dim3(a.nwaves / (PROBE_THREADS / 64)), dim3(PROBE_THREADS), 0, stream, a);
+  CUDF_HIP_TRY(hipGetLastError());
+}
+
+void launch_fjoin_sequence(size_type* out, int64_t n, hipStream_t stream)
+{
+  cudf::detail::prof::scope prof_{"fjoin_sequence", stream};
+  hipLaunchKernelGGL(k_sequence, dim3(grid_for(n)), dim3(256), 0, stream, out, n);
+  CUDF_HIP_TRY(hipGetLastError());
+}
+
+}  // namespace cudf::detail::fjoin

@@ -17,6 +17,7 @@
 
 #include <mutex>
 #include <optional>
+#include <stdexcept>
 
 namespace cudf::detail {
 
@@ -43,6 +44,20 @@ struct dev_scalar {  // one T in device memory, stream ordered
   }
 };
 
+// reference join_common_utils.hpp:25-32 (hash_join, filtered_join)
+inline double checked_load_factor(double load_factor)
+{
+  CUDF_EXPECTS(load_factor > 0, "Invalid load factor: must be greater than 0.", std::invalid_argument);
+  CUDF_EXPECTS(load_factor <= 1, "Invalid load factor: must be less than or equal to 1.", std::invalid_argument);
+  return load_factor;
+}
+inline bool same_types(table_view const& a, table_view const& b)
+{
+  if (a.num_columns() != b.num_columns()) return false;
+  for (size_type i = 0; i < a.num_columns(); ++i)
+    if (a.column(i).type() != b.column(i).type()) return false;
+  return true;
+}
 inline int32_t float_class_of(column_view const& c)
 {
   auto const cls = class_of(c.type().id());

@@ -18,27 +18,12 @@ namespace cudf {
 namespace detail {
 
 namespace {
-double checked_load_factor(double load_factor)
-{
-  CUDF_EXPECTS(load_factor > 0, "Invalid load factor: must be greater than 0.", std::invalid_argument);
-  CUDF_EXPECTS(load_factor <= 1, "Invalid load factor: must be less than or equal to 1.", std::invalid_argument);
-  return load_factor;
-}
-
 bool is_trivial_join(table_view const& left, table_view const& right, join_kind kind)
 {
   if (left.is_empty() || right.is_empty()) return true;
   if (kind == join_kind::LEFT_JOIN && left.num_rows() == 0) return true;
   if (kind == join_kind::INNER_JOIN && (left.num_rows() == 0 || right.num_rows() == 0)) return true;
   return false;
-}
-
-bool same_types(table_view const& a, table_view const& b)
-{
-  if (a.num_columns() != b.num_columns()) return false;
-  for (size_type i = 0; i < a.num_columns(); ++i)
-    if (a.column(i).type() != b.column(i).type()) return false;
-  return true;
 }
 
 // The key shape of a build table for the partitioned joins (key_layout): one key column, or two, of 4 or 8 bytes each - integers

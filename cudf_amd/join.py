@@ -1,5 +1,6 @@
 """pylibcudf.join mirror (reference python/pylibcudf/pylibcudf/join.pyx:67-112 and join.pyi): index-pair joins on key
-tables, plus a HashJoin object for cudf::hash_join (build once, probe many)."""
+tables, a HashJoin object for cudf::hash_join (build once, probe many), and left semi / anti joins with a FilteredJoin object
+for cudf::filtered_join (join.pyx:211-310)."""
 import ctypes as C
 
 from . import _lib
@@ -170,3 +171,59 @@ class HashJoin:
 
     def full_join_size(self, left_keys, stream=None):
         return self._size(left_keys, "full", stream)
+
+
+_FILTERED_KIND = {"semi": 0, "anti": 1}
+
+
+class FilteredJoin:
+    """cudf::filtered_join(right, compare_nulls, [load_factor]): built once on the right (filter) table, probed by
+    semi_join / anti_join, which return the qualifying left row indices as one INT32 Column in ascending order.
+    load_factor None selects the constructor without one."""
+
+    def __init__(self, right_keys: Table, nulls_equal: NullEquality = NullEquality.EQUAL, load_factor=None, stream=None):
+        self._right = right_keys  # keep the build table alive
+        self._h = C.c_void_p()
+        lf = -1.0 if load_factor is None else float(load_factor)
+        if load_factor is not None and lf < 0:  # (the C ABI reads a negative load factor as "none given")
+            raise ValueError("Invalid load factor: must be greater than 0.")
+        _lib.check(_lib.load().cudf_amd_filtered_join_create(right_keys._views(), right_keys.num_columns(),
+                                                             1 if nulls_equal == NullEquality.EQUAL else 0, lf,
+                                                             _stream_ptr(stream), C.byref(self._h)))
+
+    def __del__(self):
+        try:
+            if self._h:
+                # as HashJoin: the probe streams used since the last synchronisation are drained before the build state goes back
+                # to the pool on the build stream (include/cudf/join/filtered_join.hpp, Lifetime)
+                for s in getattr(self, "_probe_streams", ()):
+                    _sync_stream(s)
+                _lib.load().cudf_amd_filtered_join_destroy(self._h)
+        except Exception:
+            pass
+
+    def _probe(self, left_keys, kind, stream):
+        if not hasattr(self, "_probe_streams"):
+            self._probe_streams = []
+        if not any(s is stream for s in self._probe_streams):
+            self._probe_streams.append(stream)
+        out = C.c_void_p()
+        _lib.check(_lib.load().cudf_amd_filtered_join_probe(self._h, left_keys._views(), left_keys.num_columns(),
+                                                            _FILTERED_KIND[kind], _stream_ptr(stream), C.byref(out)))
+        return Table._from_handle(out, stream).columns()[0]
+
+    def semi_join(self, left_keys: Table, stream=None):
+        return self._probe(left_keys, "semi", stream)
+
+    def anti_join(self, left_keys: Table, stream=None):
+        return self._probe(left_keys, "anti", stream)
+
+
+def left_semi_join(left_keys: Table, right_keys: Table, nulls_equal: NullEquality = NullEquality.EQUAL, stream=None, mr=None):
+    """The left row indices that have an equal row in right_keys, ascending (pylibcudf join.left_semi_join)."""
+    return FilteredJoin(right_keys, nulls_equal, stream=stream).semi_join(left_keys, stream=stream)
+
+
+def left_anti_join(left_keys: Table, right_keys: Table, nulls_equal: NullEquality = NullEquality.EQUAL, stream=None, mr=None):
+    """The left row indices that have no equal row in right_keys, ascending (pylibcudf join.left_anti_join)."""
+    return FilteredJoin(right_keys, nulls_equal, stream=stream).anti_join(left_keys, stream=stream)

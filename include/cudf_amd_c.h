@@ -69,6 +69,8 @@ typedef struct {
 typedef struct cudf_amd_table_s* cudf_amd_table_t;
 /* Owning cudf::hash_join. */
 typedef struct cudf_amd_hash_join_s* cudf_amd_hash_join_t;
+/* Owning cudf::filtered_join. */
+typedef struct cudf_amd_filtered_join_s* cudf_amd_filtered_join_t;
 
 const char* cudf_amd_last_error(void);
 const char* cudf_amd_version(void);
@@ -175,6 +177,16 @@ cudf_amd_status cudf_amd_hash_join_finalize_full(const int32_t* const* left_part
                                                  const uint64_t* partial_sizes, int32_t num_partials,
                                                  int32_t left_num_rows, int32_t right_num_rows, void* stream,
                                                  cudf_amd_table_t* out_indices);
+
+/* ---- cudf::filtered_join (reference cpp/include/cudf/join/filtered_join.hpp): left semi and anti joins, built once on `right`
+ * (the filter table), probed many times. load_factor < 0 selects the (right, compare_nulls) constructor; otherwise it must lie in
+ * (0, 1]. The caller keeps `right`'s memory alive while the object lives. */
+cudf_amd_status cudf_amd_filtered_join_create(const cudf_amd_column_view* right_keys, int32_t num_right, int32_t nulls_equal,
+                                              double load_factor, void* stream, cudf_amd_filtered_join_t* out);
+void cudf_amd_filtered_join_destroy(cudf_amd_filtered_join_t h);
+/* kind: 0 semi_join, 1 anti_join. out_indices = table of ONE INT32 column: the qualifying left row indices, ascending. */
+cudf_amd_status cudf_amd_filtered_join_probe(cudf_amd_filtered_join_t h, const cudf_amd_column_view* left_keys, int32_t num_left,
+                                             int32_t kind, void* stream, cudf_amd_table_t* out_indices);
 
 /* ---- Arrow C Data Interface (reference cpp/include/cudf/interop.hpp: from_arrow :685-689, to_arrow_host :618-621,
  * to_arrow_schema :473-475). The structs are the ones the Arrow specification publishes.
