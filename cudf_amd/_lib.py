@@ -81,6 +81,11 @@ SYMBOLS = {
     "cudf_amd_filtered_join_create": (C.c_int, [C.POINTER(ColumnView), C.c_int32, C.c_int32, C.c_double, _P, C.POINTER(_P)]),
     "cudf_amd_filtered_join_destroy": (None, [_P]),
     "cudf_amd_filtered_join_probe": (C.c_int, [_P, C.POINTER(ColumnView), C.c_int32, C.c_int32, _P, C.POINTER(_P)]),
+    "cudf_amd_distinct_indices": (C.c_int, [C.POINTER(ColumnView), C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P, C.POINTER(_P)]),
+    "cudf_amd_distinct": (C.c_int, [C.POINTER(ColumnView), C.c_int32, C.POINTER(C.c_int32), C.c_int32, C.c_int32, C.c_int32,
+                                    C.c_int32, C.c_int32, _P, C.POINTER(_P)]),
+    "cudf_amd_distinct_count_column": (C.c_int, [C.POINTER(ColumnView), C.c_int32, C.c_int32, _P, C.POINTER(C.c_int32)]),
+    "cudf_amd_distinct_count_table": (C.c_int, [C.POINTER(ColumnView), C.c_int32, C.c_int32, _P, C.POINTER(C.c_int32)]),
     "cudf_amd_hash_partition": (C.c_int, [C.POINTER(ColumnView), C.c_int32, C.POINTER(C.c_int32), C.c_int32, C.c_int32,
                                           C.c_uint32, _P, C.POINTER(_P), C.POINTER(C.c_int32)]),
     "cudf_amd_comm_unique_id": (C.c_int, [C.POINTER(C.c_uint8)]),

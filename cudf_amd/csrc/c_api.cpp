@@ -9,6 +9,8 @@
 #include <cudf/distributed.hpp>
 #include <cudf/groupby.hpp>
 #include <cudf/partitioning.hpp>
+#include <cudf/reduction/distinct_count.hpp>
+#include <cudf/stream_compaction.hpp>
 #include <cudf/interop.hpp>
 #include <cudf/join/filtered_join.hpp>
 #include <cudf/join/hash_join.hpp>
@@ -529,6 +531,71 @@ cudf_amd_status cudf_amd_filtered_join_probe(cudf_amd_filtered_join_t h, const c
     auto t   = std::make_unique<cudf_amd_table_s>();
     t->cols.push_back(std::make_unique<cudf::column>(std::move(*idx), rmm::device_buffer{}, 0));
     *out_indices = t.release();
+  });
+}
+
+static cudf::duplicate_keep_option keep_of(int32_t keep)
+{
+  CUDF_EXPECTS(keep >= 0 && keep <= 3, "keep must be 0 (ANY), 1 (FIRST), 2 (LAST) or 3 (NONE)", std::invalid_argument);
+  return static_cast<cudf::duplicate_keep_option>(keep);
+}
+
+cudf_amd_status cudf_amd_distinct_indices(const cudf_amd_column_view* input, int32_t num_columns, int32_t keep, int32_t nulls_equal,
+                                          int32_t nans_equal, void* stream, cudf_amd_table_t* out_indices)
+{
+  return guarded([&] {
+    *out_indices = nullptr;
+    CUDF_EXPECTS(num_columns >= 0, "num_columns must not be negative", std::invalid_argument);
+    cudf::stream_ref const s{as_stream(stream)};
+    auto idx = cudf::distinct_indices(to_table(input, num_columns), keep_of(keep),
+                                      nulls_equal ? cudf::null_equality::EQUAL : cudf::null_equality::UNEQUAL,
+                                      nans_equal ? cudf::nan_equality::ALL_EQUAL : cudf::nan_equality::UNEQUAL, s);
+    auto t = std::make_unique<cudf_amd_table_s>();
+    t->cols.push_back(std::move(idx));
+    *out_indices = t.release();
+  });
+}
+
+cudf_amd_status cudf_amd_distinct(const cudf_amd_column_view* input, int32_t num_columns, const int32_t* keys, int32_t num_keys,
+                                  int32_t keep, int32_t nulls_equal, int32_t nans_equal, int32_t stable, void* stream,
+                                  cudf_amd_table_t* out_table)
+{
+  return guarded([&] {
+    *out_table = nullptr;
+    CUDF_EXPECTS(num_columns >= 0 && num_keys >= 0, "num_columns and num_keys must not be negative", std::invalid_argument);
+    CUDF_EXPECTS(num_keys == 0 || keys != nullptr, "keys must not be NULL", std::invalid_argument);
+    std::vector<cudf::size_type> k(keys, keys + num_keys);
+    cudf::stream_ref const s{as_stream(stream)};
+    auto const ne  = nulls_equal ? cudf::null_equality::EQUAL : cudf::null_equality::UNEQUAL;
+    auto const nan = nans_equal ? cudf::nan_equality::ALL_EQUAL : cudf::nan_equality::UNEQUAL;
+    auto const in  = to_table(input, num_columns);
+    auto tbl = stable ? cudf::stable_distinct(in, k, keep_of(keep), ne, nan, s) : cudf::distinct(in, k, keep_of(keep), ne, nan, s);
+    auto t   = std::make_unique<cudf_amd_table_s>();
+    t->cols  = tbl->release();
+    *out_table = t.release();
+  });
+}
+
+cudf_amd_status cudf_amd_distinct_count_column(const cudf_amd_column_view* input, int32_t null_handling, int32_t nan_handling,
+                                               void* stream, int32_t* out_count)
+{
+  return guarded([&] {
+    CUDF_EXPECTS(input != nullptr && out_count != nullptr, "input and out_count must not be NULL", std::invalid_argument);
+    cudf::stream_ref const s{as_stream(stream)};
+    *out_count = cudf::distinct_count(to_view(*input), null_handling ? cudf::null_policy::INCLUDE : cudf::null_policy::EXCLUDE,
+                                      nan_handling ? cudf::nan_policy::NAN_IS_VALID : cudf::nan_policy::NAN_IS_NULL, s);
+  });
+}
+
+cudf_amd_status cudf_amd_distinct_count_table(const cudf_amd_column_view* input, int32_t num_columns, int32_t nulls_equal,
+                                              void* stream, int32_t* out_count)
+{
+  return guarded([&] {
+    CUDF_EXPECTS(out_count != nullptr, "out_count must not be NULL", std::invalid_argument);
+    CUDF_EXPECTS(num_columns >= 0, "num_columns must not be negative", std::invalid_argument);
+    cudf::stream_ref const s{as_stream(stream)};
+    *out_count = cudf::distinct_count(to_table(input, num_columns),
+                                      nulls_equal ? cudf::null_equality::EQUAL : cudf::null_equality::UNEQUAL, s);
   });
 }
 

@@ -14,25 +14,37 @@ namespace cudf {
 namespace detail {
 
 namespace {
-// Left rows per wave chunk: at most 8192 waves (32 per CU), chunks of >= 4096 rows, a multiple of 512 (pass 1 tests 8 x 64 rows
-// at a time); the number of waves a multiple of 16 (the LDS probe's workgroup).
-struct geometry {
-  int32_t nwaves;
-  int64_t chunk;
-};
-geometry geometry_of(int64_t n)
-{
-  int64_t waves       = std::clamp<int64_t>((n + 4095) / 4096, 16, 8192);
-  int64_t const chunk = ((n + waves - 1) / waves + 511) / 512 * 512;
-  waves               = ((n + chunk - 1) / chunk + 15) / 16 * 16;
-  return {static_cast<int32_t>(waves), chunk};
-}
-
 std::unique_ptr<rmm::device_uvector<size_type>> no_rows(stream_ref stream, rmm::device_async_resource_ref mr)
 {
   return std::make_unique<rmm::device_uvector<size_type>>(0, stream.value(), mr);
 }
 }  // namespace
+
+namespace fjoin {
+bool valid_key_range(device_column const& c, int64_t rows, uint64_t& lo, uint64_t& range, hipStream_t s)
+{
+  bool const is_signed = c.cls == CLS_SINT;
+  auto tmp             = cudf::get_current_device_resource_ref();
+  join::join_args a{};
+  a.build.ncols  = 1;
+  a.build.nrows  = static_cast<int32_t>(rows);
+  a.build.col[0] = c;
+  a.check_nulls  = 1;
+  rmm::device_buffer mm{2 * sizeof(uint64_t), s, tmp}, d_args{sizeof(join::join_args), s, tmp};
+  join::launch_key_minmax(a, static_cast<join::join_args*>(d_args.data()), is_signed ? 1 : 0, static_cast<uint64_t*>(mm.data()), s);
+  uint64_t h[2] = {0, 0};
+  CUDF_HIP_TRY(hipMemcpyAsync(h, mm.data(), sizeof(h), hipMemcpyDeviceToHost, s));
+  CUDF_HIP_TRY(hipStreamSynchronize(s));
+  bool const any_valid = is_signed ? static_cast<int64_t>(h[0]) <= static_cast<int64_t>(h[1]) : h[0] <= h[1];
+  lo = range = 0;
+  if (!any_valid) return true;  // (no valid key: an empty range)
+  uint64_t const width = h[1] - h[0];  // exact in two's complement for either ordering
+  if (width == ~uint64_t{0}) return false;
+  lo    = h[0];
+  range = width + 1;
+  return true;
+}
+}  // namespace fjoin
 
 filtered_join_impl::filtered_join_impl(table_view const& right, null_equality compare_nulls, double load_factor, stream_ref stream,
                                        rmm::device_async_resource_ref mr)
@@ -55,7 +67,6 @@ bool filtered_join_impl::try_bitmap_build(stream_ref stream)
   device_column const& c = _build_dev.col[0];
   if (c.cls != CLS_SINT && c.cls != CLS_UINT) return false;
   hipStream_t const s   = stream.value();
-  auto tmp              = cudf::get_current_device_resource_ref();
   auto const rows       = static_cast<uint64_t>(_right.num_rows());
   bool const is_signed  = c.cls == CLS_SINT;
   uint64_t lo = 0, range = 0;
@@ -63,23 +74,7 @@ bool filtered_join_impl::try_bitmap_build(stream_ref stream)
     range = uint64_t{1} << (8 * c.width);
     lo    = is_signed ? static_cast<uint64_t>(-static_cast<int64_t>(range / 2)) : 0;
   } else {
-    join::join_args a{};
-    a.build.ncols       = 1;
-    a.build.nrows       = _right.num_rows();
-    a.build.col[0]      = c;
-    a.check_nulls       = 1;
-    rmm::device_buffer mm{2 * sizeof(uint64_t), s, tmp}, d_args{sizeof(join::join_args), s, tmp};
-    join::launch_key_minmax(a, static_cast<join::join_args*>(d_args.data()), is_signed ? 1 : 0, static_cast<uint64_t*>(mm.data()), s);
-    uint64_t h[2] = {0, 0};
-    CUDF_HIP_TRY(hipMemcpyAsync(h, mm.data(), sizeof(h), hipMemcpyDeviceToHost, s));
-    CUDF_HIP_TRY(hipStreamSynchronize(s));
-    bool const any_valid = is_signed ? static_cast<int64_t>(h[0]) <= static_cast<int64_t>(h[1]) : h[0] <= h[1];
-    if (any_valid) {  // (no valid key: an empty bitmap, range 0)
-      uint64_t const width = h[1] - h[0];  // exact in two's complement for either ordering
-      if (width == ~uint64_t{0}) return false;
-      lo    = h[0];
-      range = width + 1;
-    }
+    if (!fjoin::valid_key_range(c, _right.num_rows(), lo, range, s)) return false;
     auto const ratio    = static_cast<uint64_t>(std::clamp<int64_t>(env_i64("CUDF_AMD_FJOIN_DENSE_RATIO", 32), 0, int64_t{1} << 32));
     auto const max_bits = static_cast<uint64_t>(std::max<int64_t>(env_i64("CUDF_AMD_FJOIN_DENSE_MAX_BITS", int64_t{1} << 31), 0));
     if (range > max_bits || range > ratio * rows) return false;
@@ -155,7 +150,7 @@ std::unique_ptr<rmm::device_uvector<size_type>> filtered_join_impl::probe(table_
   }
   validate_probe(left);
   auto tmp           = cudf::get_current_device_resource_ref();
-  geometry const g   = geometry_of(n);
+  fjoin::geometry const g = fjoin::geometry_of(n);
   fjoin::probe_args a{};
   a.probe          = make_device_table(left);
   a.anti           = anti ? 1 : 0;

@@ -16,6 +16,7 @@
 #include <cudf/join/filtered_join.hpp>
 
 #include <hip/hip_runtime.h>
+#include <algorithm>
 #include <cstdint>
 
 namespace cudf::detail {
@@ -69,6 +70,20 @@ struct probe_args {
   uint64_t out_capacity;
 };
 
+// Rows per wave chunk of pass 1 and of the compaction: at most 8192 waves (32 per CU), chunks of >= 4096 rows, a multiple of 512
+// (pass 1 tests 8 x 64 rows at a time); the number of waves a multiple of 16 (the LDS probe's workgroup).
+struct geometry {
+  int32_t nwaves;
+  int64_t chunk;
+};
+inline geometry geometry_of(int64_t n)
+{
+  int64_t waves       = std::clamp<int64_t>((n + 4095) / 4096, 16, 8192);
+  int64_t const chunk = ((n + waves - 1) / waves + 511) / 512 * 512;
+  waves               = ((n + chunk - 1) / chunk + 15) / 16 * 16;
+  return {static_cast<int32_t>(waves), chunk};
+}
+
 void launch_bitmap_build(bitmap_args const& a, hipStream_t stream);
 void launch_set_build(set_args const& a, hipStream_t stream);
 // pass 1; lds: the bitmap is copied to LDS by every workgroup (a.bm.range <= lds_bits_max())
@@ -78,6 +93,9 @@ void launch_set_probe(probe_args const& a, hipStream_t stream);
 void launch_fjoin_compact(probe_args const& a, hipStream_t stream);
 // out[i] = i for i < n
 void launch_fjoin_sequence(size_type* out, int64_t n, hipStream_t stream);
+// [lo, lo + range): the valid keys of integer column c (SINT: compared signed), from launch_key_minmax; synchronises `s`. range 0:
+// no valid key. false: the keys span all 2^64 values.
+bool valid_key_range(device_column const& c, int64_t rows, uint64_t& lo, uint64_t& range, hipStream_t s);
 // bits of the largest bitmap the LDS probe takes (the kernel's dynamic LDS)
 uint64_t lds_bits_max();
 

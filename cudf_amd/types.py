@@ -47,6 +47,24 @@ class NullEquality(IntEnum):
     UNEQUAL = 1
 
 
+class NanPolicy(IntEnum):
+    NAN_IS_NULL = 0
+    NAN_IS_VALID = 1
+
+
+class NanEquality(IntEnum):
+    ALL_EQUAL = 0
+    UNEQUAL = 1
+
+
+class DuplicateKeepOption(IntEnum):
+    """cudf::duplicate_keep_option (reference stream_compaction.hpp; pylibcudf.stream_compaction.DuplicateKeepOption)."""
+    KEEP_ANY = 0
+    KEEP_FIRST = 1
+    KEEP_LAST = 2
+    KEEP_NONE = 3
+
+
 class Sorted(IntEnum):
     NO = 0
     YES = 1

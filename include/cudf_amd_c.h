@@ -188,6 +188,24 @@ void cudf_amd_filtered_join_destroy(cudf_amd_filtered_join_t h);
 cudf_amd_status cudf_amd_filtered_join_probe(cudf_amd_filtered_join_t h, const cudf_amd_column_view* left_keys, int32_t num_left,
                                              int32_t kind, void* stream, cudf_amd_table_t* out_indices);
 
+/* ---- cudf::distinct_indices / distinct / stable_distinct (reference cpp/include/cudf/stream_compaction.hpp) and cudf::distinct_count
+ * (reference cpp/include/cudf/reduction/distinct_count.hpp). keep: cudf::duplicate_keep_option (0 ANY, 1 FIRST, 2 LAST, 3 NONE);
+ * nulls_equal: 1 = null_equality::EQUAL, 0 = UNEQUAL; nans_equal: 1 = nan_equality::ALL_EQUAL, 0 = UNEQUAL.
+ * cudf_amd_distinct_indices: every column is a key; out_indices = table of ONE INT32 column, the surviving rows, ascending.
+ * cudf_amd_distinct: every column of `input` gathered at the surviving rows of the key columns `keys` (indices into `input`; one
+ * outside it returns CUDF_AMD_OUT_OF_RANGE); stable: 0 = distinct, 1 = stable_distinct (input order).
+ * cudf_amd_distinct_count_column: null_handling = cudf::null_policy (0 EXCLUDE, 1 INCLUDE), nan_handling = cudf::nan_policy
+ * (0 NAN_IS_NULL, 1 NAN_IS_VALID). cudf_amd_distinct_count_table: the distinct rows of the table. */
+cudf_amd_status cudf_amd_distinct_indices(const cudf_amd_column_view* input, int32_t num_columns, int32_t keep, int32_t nulls_equal,
+                                          int32_t nans_equal, void* stream, cudf_amd_table_t* out_indices);
+cudf_amd_status cudf_amd_distinct(const cudf_amd_column_view* input, int32_t num_columns, const int32_t* keys, int32_t num_keys,
+                                  int32_t keep, int32_t nulls_equal, int32_t nans_equal, int32_t stable, void* stream,
+                                  cudf_amd_table_t* out_table);
+cudf_amd_status cudf_amd_distinct_count_column(const cudf_amd_column_view* input, int32_t null_handling, int32_t nan_handling,
+                                               void* stream, int32_t* out_count);
+cudf_amd_status cudf_amd_distinct_count_table(const cudf_amd_column_view* input, int32_t num_columns, int32_t nulls_equal,
+                                              void* stream, int32_t* out_count);
+
 /* ---- Arrow C Data Interface (reference cpp/include/cudf/interop.hpp: from_arrow :685-689, to_arrow_host :618-621,
  * to_arrow_schema :473-475). The structs are the ones the Arrow specification publishes.
  * cudf_amd_from_arrow: host Arrow struct array (one child per column) -> owning device table; the input is not
