@@ -1,4 +1,4 @@
-"""cudf::distributed (cudf_amd/csrc/distributed/shuffle.hip) with peers beyond one non-null int64 key: the four collectives
+"""cudf::distributed (cudf_amd/csrc/distributed/) with peers beyond one non-null int64 key: the four collectives
 (shuffle, shuffle_groupby, combine_groupby, shuffle_join) on loopback worlds of 2, 4 and 8 virtual ranks, checked against the CPU
 oracle run on the concatenation of all shards.
 

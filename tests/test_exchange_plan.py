@@ -1,4 +1,4 @@
-"""Host-side bookkeeping of the in-library exchange (cudf::distributed::plan_exchange, cudf_amd/csrc/distributed/shuffle.hip):
+"""Host-side bookkeeping of the in-library exchange (cudf::distributed::plan_exchange, cudf_amd/csrc/distributed/shuffle.cpp):
 what a rank receives from each peer, where the slices start in its receive buffers, and how many rounds of bounded messages every
 rank runs - checked for world sizes 2..8 WITHOUT a GPU (pure host arithmetic behind the C ABI). The loop that consumes this plan
 runs with real peers in tests/test_loopback_gpu.py."""

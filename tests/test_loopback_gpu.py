@@ -1,4 +1,4 @@
-"""The in-library exchange (cudf_amd/csrc/distributed/shuffle.hip) run WITH PEERS on one GPU: V virtual ranks of a loopback
+"""The in-library exchange (cudf_amd/csrc/distributed/) run WITH PEERS on one GPU: V virtual ranks of a loopback
 communicator (include/cudf/distributed.hpp `transport`), one host thread and one HIP stream per rank. The same code drives RCCL on
 a multi-GPU node; here sends and receives are matched into device copies at group_end, so the per-peer Send / Recv loop, the
 count matrix, the receive offsets and the rounds of bounded messages all execute with world sizes 2, 4 and 8.
