@@ -134,6 +134,35 @@ __device__ __forceinline__ uint64_t normalize_key_bits(uint64_t bits, int32_t cl
   return bits;
 }
 
+// The low `width` bytes of `raw` as a signed integer of 64 bits.
+__device__ __forceinline__ int64_t sign_extend(uint64_t raw, int32_t width)
+{
+  int const sh = 64 - 8 * width;
+  return static_cast<int64_t>(raw << sh) >> sh;
+}
+
+// Order-preserving word of an element's bits: unsigned comparison of words == ascending order of values. Signed integers with the
+// sign bit flipped, floats by sign-magnitude with every NaN made the canonical quiet NaN (above +inf). -0 stays below +0, so the
+// word is reversible; a caller that wants them equal (sort keys) passes normalize_key_bits(raw, cls).
+__device__ __forceinline__ uint64_t ordered_word(uint64_t raw, int32_t cls, int32_t width)
+{
+  switch (cls) {
+    case CLS_SINT: return static_cast<uint64_t>(sign_extend(raw, width)) ^ 0x8000000000000000ull;
+    case CLS_BOOL: return raw != 0;
+    case CLS_F32: {
+      uint32_t b = static_cast<uint32_t>(raw);
+      if ((b & 0x7fffffffu) > 0x7f800000u) b = 0x7fc00000u;
+      return b ^ ((b >> 31) ? 0xffffffffu : 0x80000000u);
+    }
+    case CLS_F64: {
+      uint64_t b = raw;
+      if ((b & 0x7fffffffffffffffull) > 0x7ff0000000000000ull) b = 0x7ff8000000000000ull;
+      return b ^ ((b >> 63) ? 0xffffffffffffffffull : 0x8000000000000000ull);
+    }
+    default: return raw;
+  }
+}
+
 // Element converted to its 8-byte accumulator class: SINT -> sign-extended int64, UINT -> zero-extended,
 // BOOL -> 0/1, F32/F64 -> double bits (targets: reference detail/aggregation/aggregation.hpp:878-978).
 __device__ __forceinline__ uint64_t col_load_acc_bits(device_column const& c, int64_t i)

@@ -177,9 +177,13 @@ __global__ void __launch_bounds__(256) k_arg_finish(arg_pass a)
   }
 }
 
-unsigned blocks_of(int64_t n) { return static_cast<unsigned>(std::max<int64_t>((n + 255) / 256, 1)); }
 bool is_arg(aggregation::Kind k) { return k == aggregation::ARGMIN || k == aggregation::ARGMAX; }
 }  // namespace
+
+void fill_i32(int32_t* out, int64_t n, int32_t v, hipStream_t s)
+{
+  hipLaunchKernelGGL(k_fill_i32, dim3(blocks_of(n)), dim3(256), 0, s, out, n, v);
+}
 
 std::optional<std::pair<std::unique_ptr<table>, std::vector<aggregation_result>>> arg_by_lookup(table_view const& keys, null_policy include_null_keys,
                                                                                               std::span<aggregation_request const> requests,
@@ -282,8 +286,7 @@ std::optional<std::pair<std::unique_ptr<table>, std::vector<aggregation_result>>
                                           rmm::device_buffer{}, 0);
       a.out[e]       = index[e]->mutable_view().data<int32_t>();
     }
-    hipLaunchKernelGGL(k_fill_i32, dim3(blocks_of(static_cast<int64_t>(entries))), dim3(256), 0, s, a.index, static_cast<int64_t>(entries),
-                       std::numeric_limits<int32_t>::max());
+    fill_i32(a.index, static_cast<int64_t>(entries), std::numeric_limits<int32_t>::max(), s);
     CUDF_HIP_TRY(hipMemsetAsync(a.best, 0, entries * sizeof(uint64_t), s));
     hipLaunchKernelGGL(k_arg_fill, dim3(blocks_of(G)), dim3(256), 0, s, a);
     {

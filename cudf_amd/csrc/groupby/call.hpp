@@ -17,6 +17,7 @@
 #include <cudf/null_mask.hpp>
 #include <cudf/utilities/error.hpp>
 
+#include <algorithm>
 #include <chrono>
 #include <optional>
 #include <span>
@@ -158,7 +159,7 @@ host_plan build_plan(table_view const& keys, null_policy policy, std::span<aggre
 // Heavy-hitter handling covers plans whose accumulators are SUMs of the single value column and row COUNTs (no nulls).
 bool hot_plan_ok(plan_dev const& p);
 bool is_engine_kind(aggregation::Kind k);
-// MEDIAN / QUANTILE / NUNIQUE / NTH_ELEMENT: served by the sort-based groupby (sort_groupby.hip)
+// MEDIAN / QUANTILE / NUNIQUE / NTH_ELEMENT: served by the sort-based groupby (sort_aggregate.hip)
 inline bool is_sort_kind(aggregation::Kind k)
 {
   return k == aggregation::MEDIAN || k == aggregation::QUANTILE || k == aggregation::NUNIQUE || k == aggregation::NTH_ELEMENT;
@@ -169,7 +170,7 @@ std::optional<std::pair<std::unique_ptr<table>, std::vector<aggregation_result>>
                                                                                               std::span<aggregation_request const> requests,
                                                                                               stream_ref stream, rmm::device_async_resource_ref mr,
                                                                                               hash_path* path);
-// (sort_groupby.hip) the number of runs of equal adjacent key rows, nulls equal nulls
+// (sort_helper.hip) the number of runs of equal adjacent key rows, nulls equal nulls
 int64_t count_key_runs(table_view const& keys, stream_ref stream);
 // The sort-based groupby (reference cpp/src/groupby/sort/aggregate.cpp:798-830, sort_helper.cu): radix-sorts the rows by key,
 // labels the groups and serves every request of the call; the unique keys come back in ascending order, nulls last.
@@ -177,6 +178,10 @@ std::pair<std::unique_ptr<table>, std::vector<aggregation_result>> sort_aggregat
                                                                                   bool keys_are_sorted,
                                                                                   std::span<aggregation_request const> requests,
                                                                                   stream_ref stream, rmm::device_async_resource_ref mr);
+// workgroups of 256 threads that cover n elements (at least one)
+inline unsigned blocks_of(int64_t n) { return static_cast<unsigned>(std::max<int64_t>((n + 255) / 256, 1)); }
+// (arg_lookup.hip) out[0 .. n) = v
+void fill_i32(int32_t* out, int64_t n, int32_t v, hipStream_t s);
 double hyperloglog_estimate(std::vector<uint32_t> const& regs);
 // Page-locked host staging for a call's small read-backs (per thread; the two buffers stay valid next to each other).
 int32_t* pinned_ints(std::size_t count);

@@ -1,19 +1,15 @@
 // SPDX-License-Identifier: Apache-2.0
-// The sort helper shared by the sort-based aggregate (sort_groupby.hip) and the scans (scan_groupby.hip): the reference's
-// sort_groupby_helper (cpp/include/cudf/detail/groupby/sort_helper.hpp) built on the stable LSD radix sort of sort_groupby.hip.
-// One definition of the sorter and of the helper lives in sort_groupby.hip; this header only declares them.
+// The sort helper shared by the sort-based aggregate (sort_aggregate.hip) and the scans (scan_groupby.hip): the reference's
+// sort_groupby_helper (cpp/include/cudf/detail/groupby/sort_helper.hpp) built on the radix sort of radix_sort.hpp, and the device
+// idioms both sides share. The definitions are in sort_helper.hip.
 #pragma once
-#include "call.hpp"
+#include "radix_sort.hpp"
 
 #include <cudf/table/table_view.hpp>
 
-#include <hip/hip_runtime.h>
-
-#include <algorithm>
 #include <map>
 #include <optional>
 #include <tuple>
-#include <utility>
 
 namespace cudf::groupby::detail {
 
@@ -21,30 +17,30 @@ namespace cudf::groupby::detail {
 // (NaN above every number and all NaNs one value, -0 == +0: cpp/include/cudf/detail/row_operator/lexicographic.cuh)
 __device__ __forceinline__ uint64_t sortable_word(cudf::detail::device_column const& c, int64_t row)
 {
-  using namespace cudf::detail;
-  uint64_t const raw = col_load_bits(c, row);
-  switch (c.cls) {
-    case CLS_SINT: {
-      int const sh = 64 - 8 * c.width;
-      return static_cast<uint64_t>(static_cast<int64_t>(raw << sh) >> sh) ^ 0x8000000000000000ull;
-    }
-    case CLS_BOOL: return raw != 0;
-    case CLS_F32: {
-      uint32_t b = static_cast<uint32_t>(normalize_key_bits(raw, CLS_F32));
-      return b ^ ((b >> 31) ? 0xffffffffu : 0x80000000u);
-    }
-    case CLS_F64: {
-      uint64_t b = normalize_key_bits(raw, CLS_F64);
-      return b ^ ((b >> 63) ? 0xffffffffffffffffull : 0x8000000000000000ull);
-    }
-    default: return raw;
-  }
+  return cudf::detail::ordered_word(cudf::detail::normalize_key_bits(cudf::detail::col_load_bits(c, row), c.cls), c.cls, c.width);
 }
 
-inline unsigned blocks_of(int64_t n) { return static_cast<unsigned>(std::max<int64_t>((n + 255) / 256, 1)); }
+// are the values of rows a and b equal (nulls equal nulls)?
+__device__ __forceinline__ bool same_value(cudf::detail::device_column const& c, uint32_t a, bool a_valid, uint32_t b)
+{
+  return a_valid == cudf::detail::col_is_valid(c, b) && (!a_valid || sortable_word(c, a) == sortable_word(c, b));
+}
 
-// out[0 .. n) = exclusive prefix sums of in[0 .. n); *total (device, optional) = the sum. in == out is allowed.
-void exclusive_scan(uint32_t const* in, uint32_t* out, int64_t n, uint32_t* total, scratch& sc, hipStream_t s);
+// One element (e of n) per lane: writes the two 32-bit mask words of this wave's 64 elements and adds their nulls to *null_count.
+// Every lane of the wave calls it.
+__device__ __forceinline__ void store_wave_validity(bool valid, int64_t e, int64_t n, bitmask_type* mask, int32_t* null_count)
+{
+  uint64_t const m = __ballot(valid);
+  int const lane   = threadIdx.x & 63;
+  int64_t const w0 = (e - lane) >> 5;  // first mask word of this wave's 64 elements
+  if (lane == 0 && e < n) {
+    cudf::detail::gstore(mask + w0, static_cast<bitmask_type>(m));
+    int64_t const live  = n - e < 64 ? n - e : 64;
+    int32_t const nulls = static_cast<int32_t>(live) - __popcll(m);
+    if (nulls) atomicAdd(null_count, nulls);
+  }
+  if (lane == 32 && e < n) cudf::detail::gstore(mask + w0 + 1, static_cast<bitmask_type>(m >> 32));
+}
 
 // The key order, the group labels and offsets, and per values column the order inside the groups.
 struct helper {
@@ -64,7 +60,7 @@ struct helper {
   helper(table_view const& k, hipStream_t stream);
 
   // inner_values: a values column whose order INSIDE the groups is wanted and nobody needs the rows of a group in their original
-  // order: its words are sorted first, the key columns after them (see sort_groupby.hip).
+  // order: its words are sorted first, the key columns after them (see sort_helper.hip).
   void build(bool exclude_null_keys, bool presorted, column_view const* inner_values = nullptr);
 
   // rows in (label, null, value) order (reference sort_helper.cu:205-225 sorted_values, and the (label, value) sort of

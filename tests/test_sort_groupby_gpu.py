@@ -1,4 +1,4 @@
-"""GPU parity tests for the sort-based groupby (cudf_amd/csrc/groupby/sort_groupby.hip) through the C ABI: the kinds the hash
+"""GPU parity tests for the sort-based groupby (cudf_amd/csrc/groupby/sort_aggregate.hip) through the C ABI: the kinds the hash
 tables cannot serve (NTH_ELEMENT, NUNIQUE, MEDIAN, QUANTILE; reference cpp/src/groupby/sort/) - the reference's own KATs, then
 seeded random inputs against the CPU restatement (oracle/sort_groupby.py), then properties at sizes the restatement is too slow
 for."""
