@@ -1,5 +1,5 @@
 """Times the sort-based groupby (MEDIAN / NTH_ELEMENT / NUNIQUE) on the headline shape's keys and prints the library's per-kernel
-profile. usage: python bench_micro/sort_groupby_bench.py [rows] [groups] [key dtype int32|int64] [kinds median,nth,nunique,sum]"""
+profile. usage: python bench_micro/sort_groupby_bench.py [rows] [groups] [key dtype int32|int64|float64] [kinds median,nth,nunique,sum]"""
 import os
 import sys
 import time
@@ -15,11 +15,11 @@ from cudf_amd.types import NullPolicy
 
 n = int(sys.argv[1]) if len(sys.argv) > 1 else 100_000_000
 groups = int(sys.argv[2]) if len(sys.argv) > 2 else 1_000_000
-kdt = {"int32": torch.int32, "int64": torch.int64}[sys.argv[3] if len(sys.argv) > 3 else "int64"]
+kdt = {"int32": torch.int32, "int64": torch.int64, "float64": torch.float64}[sys.argv[3] if len(sys.argv) > 3 else "int64"]
 kinds = (sys.argv[4] if len(sys.argv) > 4 else "median").split(",")
 dev = torch.device("cuda", 0)
 g = torch.Generator(device=dev).manual_seed(3)
-k = torch.randint(0, groups, (n,), generator=g, device=dev, dtype=kdt)
+k = torch.randint(0, groups, (n,), generator=g, device=dev, dtype=torch.int64 if kdt.is_floating_point else kdt).to(kdt)
 v = torch.rand(n, generator=g, device=dev, dtype=torch.float64)
 kc, vc = cudf_amd.Column.from_torch(k), cudf_amd.Column.from_torch(v)
 make = {"median": agg.median, "nth": lambda: agg.nth_element(0), "nunique": agg.nunique, "sum": agg.sum,

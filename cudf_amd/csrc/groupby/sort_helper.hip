@@ -51,6 +51,26 @@ __global__ void __launch_bounds__(256) k_labels(uint32_t const* flags, uint32_t 
   }
 }
 
+// first_row[label] = the smallest row of the group: where the key order is not the input order inside a group (a values column sorted
+// ahead of the keys), the group's key is still that of its first row in input order, as the reference's stable sort returns it.
+// A group's positions are adjacent, so the lanes of a wave reduce per group and the last lane of each group's stretch adds its minimum.
+__global__ void __launch_bounds__(256) k_first_rows_min(int32_t const* labels, uint32_t const* order, int64_t nk, int32_t* first_row)
+{
+  int64_t const i   = static_cast<int64_t>(blockIdx.x) * 256 + threadIdx.x;
+  int const lane    = threadIdx.x & 63;
+  bool const active = i < nk;
+  int32_t const g   = active ? gload(labels + i) : -1;
+  int32_t row       = active ? static_cast<int32_t>(gload(order + i)) : 0x7fffffff;
+#pragma unroll
+  for (int o = 1; o < 64; o <<= 1) {
+    int32_t const og = __shfl_up(g, o, 64);
+    int32_t const orow = __shfl_up(row, o, 64);
+    if (lane >= o && og == g && orow < row) row = orow;
+  }
+  int32_t const next = __shfl_down(g, 1, 64);
+  if (active && (lane == 63 || next != g)) atomicMin(first_row + g, row);
+}
+
 __global__ void __launch_bounds__(256) k_valid_flags(device_column col, uint32_t const* order, int64_t nk, uint32_t* flags)
 {
   int64_t const i = static_cast<int64_t>(blockIdx.x) * 256 + threadIdx.x;
@@ -151,6 +171,15 @@ void helper::build(bool exclude_null_keys, bool presorted, column_view const* in
   first_row = keep.alloc<int32_t>(static_cast<std::size_t>(G));
   hipLaunchKernelGGL(k_labels, dim3(blocks_of(nk)), dim3(256), 0, s, flags, before, order, nk, labels, offsets, first_row);
   fill_i32(offsets + G, 1, static_cast<int32_t>(nk), s);
+  // equal keys of these classes may differ in their bits (-0.0 and 0.0, the NaNs, the non-zero bools): which row represents the group
+  // shows in the unique keys
+  bool const equal_keys_may_differ = std::any_of(dkeys.col, dkeys.col + dkeys.ncols, [](auto const& c) {
+    return c.cls == cudf::detail::CLS_F32 || c.cls == cudf::detail::CLS_F64 || c.cls == cudf::detail::CLS_BOOL;
+  });
+  if (_value_orders_in_key_order.has_value() && equal_keys_may_differ) {
+    prof::scope p_{"sort_first_rows", s};
+    hipLaunchKernelGGL(k_first_rows_min, dim3(blocks_of(nk)), dim3(256), 0, s, labels, order, nk, first_row);
+  }
   CUDF_HIP_TRY(hipGetLastError());
 }
 

@@ -52,7 +52,7 @@ struct helper {
   uint32_t* order{nullptr};     // position in key order -> row, nk used
   int32_t* labels{nullptr};     // per position
   int32_t* offsets{nullptr};    // G + 1
-  int32_t* first_row{nullptr};  // per group: a row holding its key
+  int32_t* first_row{nullptr};  // per group: the first row of the input that holds its key
   bool identity_order{false};   // order[i] == i for every i < nk == n (pre-sorted keys, nothing dropped)
   scratch keep;                 // the arrays above
   hipStream_t s;

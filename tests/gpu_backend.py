@@ -60,8 +60,14 @@ def make_aggregation(k):
 def groupby(keys, requests, include_null_keys=False, keys_are_sorted=False):
     global last_path
     from cudf_amd.types import Sorted
+    uploaded = {}  # one host column object named by two requests is ONE device column, as a caller holding one column would pass it
+
+    def values_column(v):
+        if id(v) not in uploaded:
+            uploaded[id(v)] = to_device(v)
+        return uploaded[id(v)]
     kt = cudf_amd.Table([to_device(k) for k in keys])
-    reqs = [gb.GroupByRequest(to_device(v), [make_aggregation(k) for k in kinds]) for v, kinds in requests]
+    reqs = [gb.GroupByRequest(values_column(v), [make_aggregation(k) for k in kinds]) for v, kinds in requests]
     g = gb.GroupBy(kt, NullPolicy.INCLUDE if include_null_keys else NullPolicy.EXCLUDE, Sorted.YES if keys_are_sorted else Sorted.NO)
     ukeys, results = g.aggregate(reqs)
     last_path = g.last_path

@@ -42,9 +42,9 @@ SORT_KINDS = [{"kind": "nth_element", "n": 0}, {"kind": "nth_element", "n": 1, "
               {"kind": "quantile", "quantiles": [0.5, 0.125], "interpolation": "nearest_half_up"}]
 
 
-def _compare(got, exp, float_rtol=0.0):
-    """float_rtol: order-dependent float results of the hash kinds (sums of squares, variance ... accumulated by unordered atomics on the
-    device, in row order by oracle.c) are compared to this relative error of the column's largest magnitude instead of 4 ulps."""
+def _compare(got, exp, atols=None):
+    """atols: per request and aggregation, None or one absolute bound per group (_hash_kind_atols) for the order-dependent float results
+    of the hash kinds; everything else is held to kat's rule (integers exact, floats to 4 ulps)."""
     (gk, gr), (ek, er) = got, exp
     assert len(gk) == len(ek)
     for a, e in zip(gk, ek):
@@ -52,11 +52,43 @@ def _compare(got, exp, float_rtol=0.0):
     for r, (ga, ea) in enumerate(zip(gr, er)):
         assert len(ga) == len(ea)
         for j, (a, e) in enumerate(zip(ga, ea)):
-            atol = 0.0
-            if float_rtol and not isinstance(e[0], tuple) and np.asarray(e[0]).dtype.kind == "f" and len(e[0]):
-                finite = np.asarray(e[0])[np.isfinite(e[0])]
-                atol = float_rtol * (float(np.abs(finite).max()) if len(finite) else 0.0)
+            atol = atols[r][j] if atols is not None and atols[r][j] is not None else 0.0
             kat.compare_columns(a, e, f"request {r} aggregation {j}", atol)
+
+
+def _hash_kind_atols(SG, keys, requests, include):
+    """How far two correct results of a hash kind may lie apart, per GROUP and from the INPUTS alone: the device accumulates with unordered
+    atomics, oracle.c in row order. With m = the group's valid rows and vmax = its largest finite magnitude, the bounds are those of the
+    hash fuzz (tests/test_groupby_gpu.py): a sum of m terms of magnitude <= t in any order is off by at most kat.sum_atol(m, t) =
+    m^2 * eps * t; SUM has t = vmax, SUM_OF_SQUARES t = vmax^2, MEAN divides SUM's bound by m; M2 = ssq - s * s / m stays within
+    8 * eps * m * vmax^2 plus the bound of ssq, VARIANCE divides that by m - 1. STD: |sqrt(a) - sqrt(b)| <= sqrt(|a - b|), and also
+    <= |a - b| / sqrt(max(a, b)) with max(a, b) >= the group's variance (numpy, two passes over the inputs) less the variance bound -
+    the smaller of the two. PRODUCT: m - 1 roundings of relative size eps on either side, 2 * m * eps * prod|v|.
+    Integer sums and means are exact. None: no allowance (kat's 4-ulp rule alone)."""
+    h = SG.SortHelper(keys, include)
+    first = h.offsets[:-1]
+    eps = np.finfo(np.float64).eps
+    out = []
+    for v, aggs in requests:
+        data, valid = SG._logical(v)
+        is_f = data.dtype.kind == "f"
+        d = data.astype(np.float64)[h.order]
+        ok = valid[h.order] & np.isfinite(d)
+        mag = np.where(ok, np.abs(d), 0.0)
+        m = np.maximum(np.add.reduceat(valid[h.order].astype(np.float64), first), 1.0)
+        vmax = np.maximum.reduceat(mag, first)
+        sums = lambda t: np.array([kat.sum_atol(a, b) for a, b in zip(m, t)])
+        mean = np.add.reduceat(np.where(ok, d, 0.0), first) / m
+        var = np.add.reduceat(np.where(ok, (d - np.repeat(mean, np.diff(h.offsets))) ** 2, 0.0), first) / np.maximum(m - 1.0, 1.0)
+        m2_atol = 8.0 * eps * m * vmax * vmax + (sums(vmax * vmax) if is_f else 0.0)
+        var_atol = m2_atol / np.maximum(m - 1.0, 1.0)
+        with np.errstate(divide="ignore"):
+            std_atol = np.minimum(np.sqrt(var_atol), var_atol / np.sqrt(np.maximum(var - var_atol, 0.0)))
+        per_kind = {"sum": sums(vmax) if is_f else None, "sum_of_squares": sums(vmax * vmax) if is_f else None,
+                    "mean": sums(vmax) / m if is_f else None, "m2": m2_atol, "variance": var_atol, "std": std_atol,
+                    "product": 2.0 * m * eps * np.multiply.reduceat(np.where(ok, np.abs(d), 1.0), first) if is_f else None}
+        out.append([per_kind.get(a) if isinstance(a, str) else None for a in aggs])
+    return out
 
 
 def _random_column(rng, n, type_name, distinct, null_share):
@@ -164,7 +196,8 @@ def test_hash_kinds_ride_along_with_every_result_shape(G, SG):
     for requests in ([(v, ["sum", "sum_overflow", "min", "max", "count_valid", "count_all", "mean", "argmax", "argmin", {"kind": "nunique"}])],
                      [(w, ["variance", "std", "m2", "sum_of_squares", "product", {"kind": "median"}]), (v, ["max", {"kind": "nth_element", "n": -1}])]):
         for include in (False, True):
-            _compare(G.groupby(keys, requests, include_null_keys=include), SG.groupby(keys, requests, include_null_keys=include), float_rtol=1e-9)
+            _compare(G.groupby(keys, requests, include_null_keys=include), SG.groupby(keys, requests, include_null_keys=include),
+                     _hash_kind_atols(SG, keys, requests, include))
 
 
 def test_median_at_ten_million_rows(G):
