@@ -9,12 +9,11 @@
 //   build : plain stores head[offset] = row, then one streaming count of the filled entries: as many as records <=> no key
 //           repeats (the caller runs the atomic-exchange build when they differ);
 //   probe : head[offset] per record; the pairs of a region are staged like the radix join's (k_radix_emit_staged copies them).
-// Replaces, for big inner joins on a dense unique build key, k_dense_build / k_dense_count / k_dense_retrieve (kernels.hip); the
+// Replaces, for big inner joins on a dense unique build key, k_dense_build / k_dense_count / k_dense_retrieve (dense_table_kernels.hip); the
 // reference structure is cuco::static_multiset insert + count + retrieve (cpp/src/join/hash_join/hash_join.cu:62-149).
-#include "engine.hpp"
+#include "join_device.hpp"
 #include "../common/profiler.hpp"
 
-#include <cudf/join/join.hpp>
 #include <cudf/utilities/error.hpp>
 
 #include <algorithm>
@@ -22,8 +21,6 @@
 
 namespace cudf::detail::join {
 namespace {
-
-__global__ void k_store_dense_part_args(dense_part_args v, dense_part_args* dst) { *dst = v; }
 
 // One launch serves EIGHT partitions, p0 ... p0 + 7: workgroup b the partition p0 + b % 8 (one XCD's workgroups share one
 // partition, i.e. one <= 1 MB slice of the table in that XCD's 4 MB L2), within it the regions s = b / 8, b / 8 + gridDim.x / 8, ...
@@ -145,8 +142,6 @@ __global__ void __launch_bounds__(256) k_dense_part_lookup(dense_part_args const
   __syncthreads();
   if (threadIdx.x == 0) a.pair_counts[blockIdx.x] = s_cursor;
 }
-
-__global__ void k_store_dense_stage_args(dense_stage_args v, dense_stage_args* dst) { *dst = v; }
 
 // The rows' loads of one round, all issued before any of them is used: NARROW (a 4-byte key column) and MASKED (a validity mask) are
 // compile-time so that no load sits under a run-time branch, rows past the end read the last row instead of being skipped, and a row
@@ -273,7 +268,7 @@ __global__ void __launch_bounds__(256) k_dense_left_direct(dense_stage_args cons
 void launch_dense_inrange_sample(dense_stage_args const& a, dense_stage_args* d_args, int64_t samples, unsigned long long* out, hipStream_t stream)
 {
   CUDF_EXPECTS(a.keys != nullptr && out != nullptr && a.nrows >= 1 && samples >= 1 && (a.key_width == 4 || a.key_width == 8), "dense join, probe sample: arguments");
-  hipLaunchKernelGGL(k_store_dense_stage_args, dim3(1), dim3(1), 0, stream, a, d_args);
+  hipLaunchKernelGGL(k_store_args<dense_stage_args>, dim3(1), dim3(1), 0, stream, a, d_args);
   CUDF_HIP_TRY(hipMemsetAsync(out, 0, 2 * sizeof(unsigned long long), stream));
   int64_t const stride = std::max<int64_t>(1, a.nrows / samples);
   int64_t const n      = (a.nrows + stride - 1) / stride;
@@ -286,7 +281,7 @@ void launch_dense_left_direct(dense_stage_args const& a, dense_stage_args* d_arg
 {
   CUDF_EXPECTS(a.keys != nullptr && a.head != nullptr && out_probe != nullptr && out_build != nullptr && a.nrows >= 1 && (a.key_width == 4 || a.key_width == 8),
                "dense join, direct left join: arguments");
-  hipLaunchKernelGGL(k_store_dense_stage_args, dim3(1), dim3(1), 0, stream, a, d_args);
+  hipLaunchKernelGGL(k_store_args<dense_stage_args>, dim3(1), dim3(1), 0, stream, a, d_args);
   cudf::detail::prof::scope prof_{"join_retrieve", stream};
   unsigned const grid = static_cast<unsigned>(std::clamp<int64_t>((a.nrows + 2047) / 2048, 1, 8192));
   CUDF_AMD_DENSE_VARIANT(k_dense_left_direct, a, grid, stream, d_args, out_probe, out_build);
@@ -298,7 +293,7 @@ void launch_dense_probe_staged(dense_stage_args const& a, dense_stage_args* d_ar
   CUDF_EXPECTS(a.keys != nullptr && a.head != nullptr && a.stage != nullptr && a.pair_counts != nullptr && a.wave_rows >= 64 && a.wave_rows % 64 == 0 &&
                  a.nwaves >= 1 && static_cast<int64_t>(a.nwaves) * a.wave_rows >= a.nrows && (a.key_width == 4 || a.key_width == 8),
                "dense join, ordered probe: arguments");
-  hipLaunchKernelGGL(k_store_dense_stage_args, dim3(1), dim3(1), 0, stream, a, d_args);
+  hipLaunchKernelGGL(k_store_args<dense_stage_args>, dim3(1), dim3(1), 0, stream, a, d_args);
   cudf::detail::prof::scope prof_{"join_count", stream};
   CUDF_AMD_DENSE_VARIANT(k_dense_probe_staged, a, (a.nwaves + 3) / 4, stream, d_args);
   CUDF_HIP_TRY(hipGetLastError());
@@ -315,7 +310,7 @@ void launch_dense_part_store(dense_part_args const& a, dense_part_args* d_args, 
 {
   CUDF_EXPECTS(a.P >= 1 && a.S >= 1 && a.P_used >= 1 && a.P_used <= a.P && a.recs != nullptr && a.head != nullptr && a.overflow != nullptr,
                "partitioned dense join: arguments");
-  hipLaunchKernelGGL(k_store_dense_part_args, dim3(1), dim3(1), 0, stream, a, d_args);
+  hipLaunchKernelGGL(k_store_args<dense_part_args>, dim3(1), dim3(1), 0, stream, a, d_args);
   cudf::detail::prof::scope prof_{"join_build", stream};
   constexpr int G = 2;  // partitions per XCD and launch (for_each_region)
   for (int p0 = 0; p0 < a.P_used; p0 += 8 * G) hipLaunchKernelGGL(k_dense_part_store, dim3(dense_part_grid()), dim3(256), 0, stream, d_args, p0, G);
@@ -340,7 +335,7 @@ void launch_dense_part_lookup(dense_part_args const& a, dense_part_args* d_args,
   CUDF_EXPECTS(a.P >= 1 && a.S >= 1 && a.recs != nullptr && a.head != nullptr && a.overflow != nullptr && a.stage != nullptr && a.pair_counts != nullptr &&
                  a.stage_cap >= dense_part_regions_per_workgroup(a.P_used, a.S) * a.region_cap && a.P_used >= 1 && a.P_used <= a.P,
                "partitioned dense join: arguments");
-  hipLaunchKernelGGL(k_store_dense_part_args, dim3(1), dim3(1), 0, stream, a, d_args);
+  hipLaunchKernelGGL(k_store_args<dense_part_args>, dim3(1), dim3(1), 0, stream, a, d_args);
   cudf::detail::prof::scope prof_{"join_count", stream};
   CUDF_HIP_TRY(hipMemsetAsync(a.pair_counts, 0, (static_cast<std::size_t>(dense_part_grid()) + 1) * sizeof(unsigned long long), stream));
   for (int p0 = 0; p0 < a.P_used; p0 += 8) hipLaunchKernelGGL(k_dense_part_lookup, dim3(dense_part_grid()), dim3(256), 0, stream, d_args, p0);

@@ -22,7 +22,7 @@ struct join_args {
   device_table probe;
   uint64_t* table;         // capacity 8-byte slots {32-bit hash tag | build row}, walked in aligned pairs
   // Build only: BUILD_SKIP_ENTRIES advisory hints {44 hash bits | n}: "the first n steps of this hash's probe sequence are
-  // full" (kernels.hip k_build, seq_next). An insert that has walked BUILD_SKIP_AFTER steps looks its hint up and jumps
+  // full" (open_table_kernels.hip k_build, seq_next). An insert that has walked BUILD_SKIP_AFTER steps looks its hint up and jumps
   // ahead; an insert that ended further than that along its sequence leaves one.
   uint64_t* build_skip;
   uint64_t capacity;
@@ -243,14 +243,18 @@ void launch_dense_build(join_args const& a, join_args* d_args, hipStream_t strea
 // Reference: cuco::static_multiset keeps duplicates as separate entries along the probe sequence (hash_join.cu:62-99).
 std::size_t dense_csr_entries(uint64_t range);
 void launch_dense_csr(join_args const& a, join_args* d_args, int32_t* cursor, uint32_t* tile_sums, hipStream_t stream);
+// count and retrieve passes over the open-addressing table / the dense table (a.dense_head != nullptr): same arguments and outputs
 void launch_count(join_args const& a, join_args* d_args, hipStream_t stream);
-// exclusive scan of block_counts in place (block_counts[nblocks] = total pairs)
-void launch_scan(join_args const& a, hipStream_t stream);
+void launch_dense_count(join_args const& a, join_args* d_args, hipStream_t stream);
 void launch_retrieve(join_args const& a, join_args* d_args, hipStream_t stream);
-// after launch_retrieve with a.big_list != nullptr: the pairs of the work list, by the whole grid
-void launch_dense_big_emit(join_args const& a, join_args* d_args, hipStream_t stream);
-// full join: appends (JoinNoMatch, r) for every build row with build_matched[r] == 0
-void launch_complement(join_args const& a, join_args* d_args, hipStream_t stream);
+void launch_dense_retrieve(join_args const& a, join_args* d_args, hipStream_t stream);
+// after launch_dense_retrieve with big_list != nullptr: the pairs of the work list, by the whole grid (d_args: what the retrieve pass read)
+void launch_dense_big_emit(join_args* d_args, hipStream_t stream);
+// exclusive scan of counts[0, n) in place, one workgroup (pair_kernels.hip); counts[n] = their sum
+void launch_scan(unsigned long long* counts, int32_t n, hipStream_t stream);
+// full join: appends (JoinNoMatch, r) at *total for every build row r < nrows with build_matched[r] == 0
+void launch_complement(uint8_t const* build_matched, int64_t nrows, unsigned long long* total, size_type* out_probe, size_type* out_build,
+                       uint64_t out_capacity, hipStream_t stream);
 // finalize_partitioned_full_join: build_matched[r] = 1 for every r != JoinNoMatch in right_indices[0..n)
 void launch_mark_matched(size_type const* right_indices, std::size_t n, uint8_t* build_matched, hipStream_t stream);
 

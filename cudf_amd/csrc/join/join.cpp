@@ -90,15 +90,7 @@ join_index_pair append_unmatched(host_span<device_span<size_type const> const> l
   std::size_t U = 0;
   if (nr > 0) {
     dev_scalar<unsigned long long> cursor{0ull, s};
-    join_args a{};
-    a.build.nrows   = static_cast<int32_t>(nr);
-    a.build_matched = static_cast<uint8_t*>(matched.data());
-    a.total         = cursor.ptr();
-    a.out_probe     = comp_l.data();
-    a.out_build     = comp_r.data();
-    a.out_capacity  = nr;
-    rmm::device_buffer d_args{sizeof(join_args), s, tmp};
-    join::launch_complement(a, static_cast<join_args*>(d_args.data()), s);
+    join::launch_complement(static_cast<uint8_t const*>(matched.data()), static_cast<int64_t>(nr), cursor.ptr(), comp_l.data(), comp_r.data(), nr, s);
     U = static_cast<std::size_t>(cursor.value());  // (synchronises)
   }
   auto out       = alloc_pairs(P + U, s, mr);
@@ -118,10 +110,7 @@ join_index_pair append_unmatched(host_span<device_span<size_type const> const> l
 
 unsigned long long scan_total(unsigned long long* counts, int32_t n, hipStream_t s, int32_t const* d_flag, int32_t* h_flag)
 {
-  join_args sc{};
-  sc.block_counts = counts;
-  sc.nblocks      = n;
-  join::launch_scan(sc, s);
+  join::launch_scan(counts, n, s);
   unsigned long long total = 0;
   CUDF_HIP_TRY(hipMemcpyAsync(&total, counts + n, sizeof(total), hipMemcpyDeviceToHost, s));
   if (d_flag != nullptr) CUDF_HIP_TRY(hipMemcpyAsync(h_flag, d_flag, sizeof(int32_t), hipMemcpyDeviceToHost, s));

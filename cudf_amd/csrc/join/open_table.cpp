@@ -78,7 +78,9 @@ hash_join_impl::count_scratch hash_join_impl::count_pass(join_args& a, hipStream
                   rmm::device_buffer{sizeof(join_args), s, tmp}};
   a.block_counts = static_cast<unsigned long long*>(c.counts.data());
   a.match_cache  = static_cast<uint32_t*>(c.cache.data());
-  join::launch_count(a, static_cast<join_args*>(c.d_args.data()), s);
+  auto* d_args = static_cast<join_args*>(c.d_args.data());
+  if (a.dense_head != nullptr) join::launch_dense_count(a, d_args, s);  // (base_args sets dense_head from _state)
+  else join::launch_count(a, d_args, s);
   return c;
 }
 
@@ -142,11 +144,11 @@ join_index_pair hash_join_impl::probe_tables(table_view const& left, join_kind k
     a.big_count = a.big_list + 5 * static_cast<std::size_t>(join::BIG_LIST_CAP);
     CUDF_HIP_TRY(hipMemsetAsync(a.big_count, 0, sizeof(uint32_t), s));
   }
-  join::launch_retrieve(a, d_args, s);
-  if (a.big_list != nullptr) join::launch_dense_big_emit(a, d_args, s);
+  if (a.dense_head != nullptr) join::launch_dense_retrieve(a, d_args, s);
+  else join::launch_retrieve(a, d_args, s);
+  if (a.big_list != nullptr) join::launch_dense_big_emit(d_args, s);
   if (kind == join_kind::FULL_JOIN) {
-    rmm::device_buffer d_args2{sizeof(join_args), s, cudf::get_current_device_resource_ref()};
-    join::launch_complement(a, static_cast<join_args*>(d_args2.data()), s);
+    join::launch_complement(a.build_matched, _right.num_rows(), a.total, a.out_probe, a.out_build, a.out_capacity, s);
     std::size_t const total = static_cast<std::size_t>(cursor.value());
     if (total != room) {  // exact-size outputs
       auto exact = alloc_pairs(total, s, mr);

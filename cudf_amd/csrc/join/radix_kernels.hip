@@ -9,11 +9,10 @@
 // slots' state, probed in aligned pairs = one ds_read_b128) and streams the partition's probe rows past it - count pass and
 // retrieve pass (the reference's size_impl.cuh:26-61 / retrieve_impl.cuh:29-133 structure), pairs allocated from a
 // workgroup-local cursor by 64-lane ballots.
-#include "engine.hpp"
+#include "join_device.hpp"
 #include "../common/profiler.hpp"
 #include "../common/ring_scatter.hpp"
 
-#include <cudf/join/join.hpp>
 #include <cudf/utilities/error.hpp>
 
 #include <mutex>
@@ -21,11 +20,6 @@
 namespace cudf::detail::join {
 namespace {
 
-template <typename T>
-__global__ void k_store_radix_args(T v, T* dst)
-{
-  *dst = v;
-}
 __device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
 __device__ __forceinline__ uint64_t radix_hash(uint64_t key) { return mix64(0x9e3779b97f4a7c15ull ^ key); }
 // two-word keys: ONE 64-bit word that stands for the pair in the partition digits and as the LDS table's slot state (every candidate it
@@ -708,7 +702,7 @@ void launch_radix_scatter(radix_scatter_args const& a, radix_scatter_args* d_arg
       CUDF_HIP_TRY(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - static_cast<int>(attr.sharedSizeBytes)));
     }
   });
-  hipLaunchKernelGGL(k_store_radix_args<radix_scatter_args>, dim3(1), dim3(1), 0, stream, a, d_args);
+  hipLaunchKernelGGL(k_store_args<radix_scatter_args>, dim3(1), dim3(1), 0, stream, a, d_args);
   int shape = SHAPE_ANY;
   if (a.level == 1 && a.kw == 2 && !dense && a.key_class == 0 && a.key2_class == 0) {
     int const w = a.key_width * 10 + a.key2_width;
@@ -763,7 +757,7 @@ void launch_radix_join(radix_join_args const& a, radix_join_args* d_args, bool r
       CUDF_HIP_TRY(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - static_cast<int>(attr.sharedSizeBytes)));
     }
   });
-  hipLaunchKernelGGL(k_store_radix_args<radix_join_args>, dim3(1), dim3(1), 0, stream, a, d_args);
+  hipLaunchKernelGGL(k_store_args<radix_join_args>, dim3(1), dim3(1), 0, stream, a, d_args);
   cudf::detail::prof::scope prof_{retrieve ? "join_retrieve" : "join_count", stream};
   if (a.kw == 2) {
     CUDF_EXPECTS(a.b_key1 != nullptr && a.p_key1 != nullptr && static_cast<int64_t>(a.b_slices) * a.b_cap < (int64_t{1} << 31), "radix join: two-word keys");
@@ -796,7 +790,7 @@ void launch_radix_null_rows(bitmask_type const* mask, int64_t mask_offset, int64
 
 void launch_radix_emit_staged(radix_join_args const& a, radix_join_args* d_args, hipStream_t stream)
 {
-  hipLaunchKernelGGL(k_store_radix_args<radix_join_args>, dim3(1), dim3(1), 0, stream, a, d_args);
+  hipLaunchKernelGGL(k_store_args<radix_join_args>, dim3(1), dim3(1), 0, stream, a, d_args);
   cudf::detail::prof::scope prof_{"join_retrieve", stream};
   hipLaunchKernelGGL(k_radix_emit_staged, dim3(a.nparts), dim3(256), 0, stream, d_args);
   CUDF_HIP_TRY(hipGetLastError());

@@ -185,7 +185,7 @@ def test_random_multi_column_mixed_types(G, oracle, nulls_equal):
 @pytest.mark.parametrize("two_columns", [False, True])
 def test_heavily_duplicated_build_key(G, oracle, kind, two_columns):
     """One build key with 40,000 duplicates among 120,000 build rows: its entries fill the linear window of its probe
-    sequence and continue on the key's own stride trail (kernels.hip seq_next); build, count and retrieve passes must
+    sequence and continue on the key's own stride trail (open_table_kernels.hip seq_next); build, count and retrieve passes must
     walk the same sequence, neighbours of the heavy key's home slot must still be found, and the inserts must share
     their skip hints. Checked against the oracle, with a time bound (the quadratic walk took seconds)."""
     import time
@@ -463,6 +463,50 @@ def test_dense_key_join_hot_build_key(G, oracle, monkeypatch, kind):
         ctx = hj.inner_join_match_context(cudf_amd.Table([G.to_device((lk, lv))]))
         counts = ctx._match_counts.to_numpy()[0]
         assert np.array_equal(counts, np.bincount(el, minlength=nl))
+
+
+_SCAN_TILE = 8192  # words per tile of the row-list build's scan (dense_table_kernels.hip SCAN_TILE)
+
+
+@pytest.mark.parametrize("key_range,nr,nl", [(_SCAN_TILE - 2, 70_000, 20_000), (_SCAN_TILE - 1, 70_000, 20_000), (_SCAN_TILE, 70_000, 20_000),
+                                             (_SCAN_TILE * 1024 + 1, (_SCAN_TILE * 1024) // 4 + 1, 4_096)])
+def test_dense_row_lists_at_the_scan_tile_edges(G, oracle, monkeypatch, key_range, nr, nl):
+    """The row-list build of a dense table whose build keys repeat (launch_dense_csr) scans key_range + 1 count words in tiles of
+    8,192 (k_scan_u32_sums / _tiles / _apply). Ranges of 8,190 / 8,191 / 8,192 values put the scan just under, exactly at and just
+    over one tile; 8,192 * 1,024 + 1 values make 1,025 tiles, so the one workgroup that scans the tile sums goes round its 1,024-tile
+    loop a second time and uses its carry. The dense table admits a range only below max(4 * rows, 2^20): the last case has the
+    fewest build rows that pass (2,097,153). Every build key has two or more rows and both ends of the range occur. The partitioned
+    dense build is not forced off: it takes build sides from 4M rows only (CUDF_AMD_JOIN_DENSE_PART_MIN_BUILD), which none of
+    these reaches - the kernel names show that no partition pass ran."""
+    import cudf_amd
+    from cudf_amd.join import HashJoin
+    from cudf_amd.types import NullEquality
+    rng = np.random.default_rng(97)
+    lo = 1_000_000
+    assert key_range - 1 < max(4 * nr, 1 << 20)  # (the dense table's admission rule, try_dense_build)
+    if 2 * key_range <= nr:  # every value of the range twice, the rest of the rows at random
+        rk = np.concatenate([np.arange(key_range), np.arange(key_range), rng.integers(0, key_range, nr - 2 * key_range)])
+    else:  # nr // 2 distinct values, both ends among them, twice each (and one of them a third time when nr is odd)
+        inner = rng.choice(key_range - 2, nr // 2 - 2, replace=False) + 1
+        keys = np.concatenate([[0, key_range - 1], inner])
+        rk = np.concatenate([keys, keys, keys[:nr % 2]])
+    rk = rng.permutation(rk).astype(np.int64) + lo
+    assert len(rk) == nr and np.bincount(rk - lo).max() >= 2 and not (np.bincount(rk - lo) == 1).any()
+    lk = np.concatenate([rk[:nl // 2], rng.integers(-1_000, key_range + 1_000, nl - nl // 2) + lo]).astype(np.int64)
+    monkeypatch.setenv("CUDF_AMD_JOIN_DENSE_MIN_ROWS", "1")
+
+    def run():
+        hj = HashJoin(cudf_amd.Table([G.to_device(rk)]), NullEquality.UNEQUAL)
+        pl, pr = hj.inner_join(cudf_amd.Table([G.to_device(lk)]))
+        return pl.to_numpy()[0], pr.to_numpy()[0]
+    (li, ri), kernels = _kernels_of(run)
+    # the profiler counts scopes: key range + direct-address build + row-list build (launch_dense_csr: counts, the three scan kernels,
+    # fill). An open-addressing table or a dense table of unique keys would show two, so three means the row lists and their scan ran.
+    assert kernels.get("join_build", 0) == 3, kernels
+    assert not any(k.startswith("join_partition") for k in kernels), kernels  # (neither the radix join nor the partitioned dense table)
+    el, er = oracle.join([lk], [rk], nulls_equal=False, kind="inner")
+    assert len(li) == len(el)
+    assert kat.sorted_pairs(li, ri) == kat.sorted_pairs(el, er)
 
 
 @pytest.mark.parametrize("seed", range(12))
