@@ -81,6 +81,10 @@ SYMBOLS = {
     "cudf_amd_filtered_join_create": (C.c_int, [C.POINTER(ColumnView), C.c_int32, C.c_int32, C.c_double, _P, C.POINTER(_P)]),
     "cudf_amd_filtered_join_destroy": (None, [_P]),
     "cudf_amd_filtered_join_probe": (C.c_int, [_P, C.POINTER(ColumnView), C.c_int32, C.c_int32, _P, C.POINTER(_P)]),
+    "cudf_amd_distinct_hash_join_create": (C.c_int, [C.POINTER(ColumnView), C.c_int32, C.c_int32, C.c_double, _P, C.POINTER(_P)]),
+    "cudf_amd_distinct_hash_join_destroy": (None, [_P]),
+    "cudf_amd_distinct_hash_join_inner_join": (C.c_int, [_P, C.POINTER(ColumnView), C.c_int32, _P, C.POINTER(_P)]),
+    "cudf_amd_distinct_hash_join_left_join": (C.c_int, [_P, C.POINTER(ColumnView), C.c_int32, _P, C.POINTER(_P)]),
     "cudf_amd_distinct_indices": (C.c_int, [C.POINTER(ColumnView), C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P, C.POINTER(_P)]),
     "cudf_amd_distinct": (C.c_int, [C.POINTER(ColumnView), C.c_int32, C.POINTER(C.c_int32), C.c_int32, C.c_int32, C.c_int32,
                                     C.c_int32, C.c_int32, _P, C.POINTER(_P)]),

@@ -12,6 +12,7 @@
 #include <cudf/reduction/distinct_count.hpp>
 #include <cudf/stream_compaction.hpp>
 #include <cudf/interop.hpp>
+#include <cudf/join/distinct_hash_join.hpp>
 #include <cudf/join/filtered_join.hpp>
 #include <cudf/join/hash_join.hpp>
 #include <cudf/join/join.hpp>
@@ -38,6 +39,9 @@ struct cudf_amd_hash_join_s {
 };
 struct cudf_amd_filtered_join_s {
   std::unique_ptr<cudf::filtered_join> fj;
+};
+struct cudf_amd_distinct_hash_join_s {
+  std::unique_ptr<cudf::distinct_hash_join> dj;
 };
 
 namespace {
@@ -528,6 +532,47 @@ cudf_amd_status cudf_amd_filtered_join_probe(cudf_amd_filtered_join_t h, const c
     auto const l = to_table(left_keys, num_left);
     cudf::stream_ref const s{as_stream(stream)};
     auto idx = kind == 0 ? h->fj->semi_join(l, s) : h->fj->anti_join(l, s);
+    auto t   = std::make_unique<cudf_amd_table_s>();
+    t->cols.push_back(std::make_unique<cudf::column>(std::move(*idx), rmm::device_buffer{}, 0));
+    *out_indices = t.release();
+  });
+}
+
+cudf_amd_status cudf_amd_distinct_hash_join_create(const cudf_amd_column_view* right_keys, int32_t num_right, int32_t nulls_equal,
+                                                   double load_factor, void* stream, cudf_amd_distinct_hash_join_t* out)
+{
+  return guarded([&] {
+    *out          = nullptr;
+    auto const r  = to_table(right_keys, num_right);
+    auto const eq = nulls_equal ? cudf::null_equality::EQUAL : cudf::null_equality::UNEQUAL;
+    cudf::stream_ref const s{as_stream(stream)};
+    auto h = std::make_unique<cudf_amd_distinct_hash_join_s>();
+    if (load_factor < 0) h->dj = std::make_unique<cudf::distinct_hash_join>(r, eq, 0.5, s);  // (the header's default)
+    else h->dj = std::make_unique<cudf::distinct_hash_join>(r, eq, load_factor, s);
+    *out = h.release();
+  });
+}
+void cudf_amd_distinct_hash_join_destroy(cudf_amd_distinct_hash_join_t h) { delete h; }
+
+cudf_amd_status cudf_amd_distinct_hash_join_inner_join(cudf_amd_distinct_hash_join_t h, const cudf_amd_column_view* left_keys,
+                                                       int32_t num_left, void* stream, cudf_amd_table_t* out_indices)
+{
+  return guarded([&] {
+    *out_indices = nullptr;
+    CUDF_EXPECTS(h != nullptr && h->dj != nullptr, "null distinct_hash_join handle", std::invalid_argument);
+    cudf::stream_ref const s{as_stream(stream)};
+    *out_indices = indices_to_table(h->dj->inner_join(to_table(left_keys, num_left), s));
+  });
+}
+
+cudf_amd_status cudf_amd_distinct_hash_join_left_join(cudf_amd_distinct_hash_join_t h, const cudf_amd_column_view* left_keys,
+                                                      int32_t num_left, void* stream, cudf_amd_table_t* out_indices)
+{
+  return guarded([&] {
+    *out_indices = nullptr;
+    CUDF_EXPECTS(h != nullptr && h->dj != nullptr, "null distinct_hash_join handle", std::invalid_argument);
+    cudf::stream_ref const s{as_stream(stream)};
+    auto idx = h->dj->left_join(to_table(left_keys, num_left), s);
     auto t   = std::make_unique<cudf_amd_table_s>();
     t->cols.push_back(std::make_unique<cudf::column>(std::move(*idx), rmm::device_buffer{}, 0));
     *out_indices = t.release();

@@ -225,40 +225,14 @@ __global__ void __launch_bounds__(PROBE_THREADS) k_set_probe_rows(probe_args a)
 }
 
 // ------------------------------------------------------------------ pass 2: ordered compaction
-// Wave `wave` streams the mask words of its chunk, 64 at a time (one per lane), and writes the rows of the set bits at its chunk's
-// offset (counts, scanned) plus the bits before them: the words' exclusive prefix over the wave, then each word's bits below the
-// lane (mbcnt). No atomics; the output is in row order.
+// Wave `wave` writes the rows of the set bits of its chunk's mask words at their positions of the output (compact_chunk,
+// set_device.hpp). No atomics; the output is in row order.
 __global__ void __launch_bounds__(PROBE_THREADS) k_compact(probe_args a)
 {
-  int const lane      = threadIdx.x & 63;
-  int64_t const wave  = static_cast<int64_t>(blockIdx.x) * (PROBE_THREADS / 64) + (threadIdx.x >> 6);
-  int64_t const begin = wave * a.chunk;
-  int64_t const end   = a.nrows < begin + a.chunk ? a.nrows : begin + a.chunk;
-  if (begin >= end) return;
-  uint64_t base      = gload(a.counts + wave);
-  int64_t const w_end = (end + 63) >> 6;
-  for (int64_t w0 = begin >> 6; w0 < w_end; w0 += 64) {
-    uint64_t const word = w0 + lane < w_end ? gload(a.mask + w0 + lane) : 0;
-    uint32_t const c    = __popcll(word);
-    uint32_t inc        = c;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-      uint32_t const t = __shfl_up(inc, o);
-      if (lane >= o) inc += t;
-    }
-    uint32_t const exc   = inc - c;
-    uint32_t const total = __shfl(inc, 63);
-    int const nw         = static_cast<int>(w_end - w0 < 64 ? w_end - w0 : 64);
-    for (int k = 0; k < nw; ++k) {
-      uint64_t const wk = __shfl(word, k);
-      if (wk == 0) continue;  // (uniform)
-      uint32_t const at   = __shfl(exc, k);
-      uint32_t const rank = __builtin_amdgcn_mbcnt_hi(static_cast<uint32_t>(wk >> 32), __builtin_amdgcn_mbcnt_lo(static_cast<uint32_t>(wk), 0u));
-      uint64_t const o    = base + at + rank;
-      if (((wk >> lane) & 1) && o < a.out_capacity) gstore(a.out + o, static_cast<size_type>((w0 + k) * 64 + lane));
-    }
-    base += total;
-  }
+  int64_t const wave = static_cast<int64_t>(blockIdx.x) * (PROBE_THREADS / 64) + (threadIdx.x >> 6);
+  compact_chunk(a.mask, a.counts, wave, a.chunk, a.nrows, [&](uint64_t o, int64_t row) {
+    if (o < a.out_capacity) gstore(a.out + o, static_cast<size_type>(row));
+  });
 }
 
 // an empty right table: anti_join returns every left row

@@ -1,6 +1,6 @@
 """pylibcudf.join mirror (reference python/pylibcudf/pylibcudf/join.pyx:67-112 and join.pyi): index-pair joins on key
-tables, a HashJoin object for cudf::hash_join (build once, probe many), and left semi / anti joins with a FilteredJoin object
-for cudf::filtered_join (join.pyx:211-310)."""
+tables, a HashJoin object for cudf::hash_join (build once, probe many), left semi / anti joins with a FilteredJoin object
+for cudf::filtered_join (join.pyx:211-310), and a DistinctHashJoin object for cudf::distinct_hash_join (a right table of distinct rows)."""
 import ctypes as C
 
 from . import _lib
@@ -217,6 +217,49 @@ class FilteredJoin:
 
     def anti_join(self, left_keys: Table, stream=None):
         return self._probe(left_keys, "anti", stream)
+
+
+class DistinctHashJoin:
+    """cudf::distinct_hash_join(right, compare_nulls, load_factor): built once on a right table whose rows are distinct, probed by
+    inner_join -> (left_idx, right_idx), the left indices strictly ascending, and left_join -> right_idx, one entry per left row
+    (JOIN_NO_MATCH where there is no match), as INT32 Columns. load_factor None selects the constructor's default."""
+
+    def __init__(self, right_keys: Table, nulls_equal: NullEquality = NullEquality.EQUAL, load_factor=None, stream=None):
+        self._right = right_keys  # keep the build table alive
+        self._h = C.c_void_p()
+        lf = -1.0 if load_factor is None else float(load_factor)
+        if load_factor is not None and lf < 0:  # (the C ABI reads a negative load factor as "none given")
+            raise ValueError("Invalid load factor: must be greater than 0.")
+        _lib.check(_lib.load().cudf_amd_distinct_hash_join_create(right_keys._views(), right_keys.num_columns(),
+                                                                  1 if nulls_equal == NullEquality.EQUAL else 0, lf,
+                                                                  _stream_ptr(stream), C.byref(self._h)))
+
+    def __del__(self):
+        try:
+            if self._h:
+                # as HashJoin: the probe streams used since the last synchronisation are drained before the build state goes back
+                # to the pool on the build stream (include/cudf/join/distinct_hash_join.hpp, Lifetime)
+                for s in getattr(self, "_probe_streams", ()):
+                    _sync_stream(s)
+                _lib.load().cudf_amd_distinct_hash_join_destroy(self._h)
+        except Exception:
+            pass
+
+    def _probe(self, entry, left_keys, stream):
+        if not hasattr(self, "_probe_streams"):
+            self._probe_streams = []
+        if not any(s is stream for s in self._probe_streams):
+            self._probe_streams.append(stream)
+        out = C.c_void_p()
+        _lib.check(entry(self._h, left_keys._views(), left_keys.num_columns(), _stream_ptr(stream), C.byref(out)))
+        return Table._from_handle(out, stream).columns()
+
+    def inner_join(self, left_keys: Table, stream=None):
+        cols = self._probe(_lib.load().cudf_amd_distinct_hash_join_inner_join, left_keys, stream)
+        return cols[0], cols[1]
+
+    def left_join(self, left_keys: Table, stream=None):
+        return self._probe(_lib.load().cudf_amd_distinct_hash_join_left_join, left_keys, stream)[0]
 
 
 def left_semi_join(left_keys: Table, right_keys: Table, nulls_equal: NullEquality = NullEquality.EQUAL, stream=None, mr=None):

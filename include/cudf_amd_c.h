@@ -71,6 +71,8 @@ typedef struct cudf_amd_table_s* cudf_amd_table_t;
 typedef struct cudf_amd_hash_join_s* cudf_amd_hash_join_t;
 /* Owning cudf::filtered_join. */
 typedef struct cudf_amd_filtered_join_s* cudf_amd_filtered_join_t;
+/* Owning cudf::distinct_hash_join. */
+typedef struct cudf_amd_distinct_hash_join_s* cudf_amd_distinct_hash_join_t;
 
 const char* cudf_amd_last_error(void);
 const char* cudf_amd_version(void);
@@ -187,6 +189,20 @@ void cudf_amd_filtered_join_destroy(cudf_amd_filtered_join_t h);
 /* kind: 0 semi_join, 1 anti_join. out_indices = table of ONE INT32 column: the qualifying left row indices, ascending. */
 cudf_amd_status cudf_amd_filtered_join_probe(cudf_amd_filtered_join_t h, const cudf_amd_column_view* left_keys, int32_t num_left,
                                              int32_t kind, void* stream, cudf_amd_table_t* out_indices);
+
+/* ---- cudf::distinct_hash_join (reference cpp/include/cudf/join/distinct_hash_join.hpp): inner and left joins on a right table
+ * whose rows are distinct, built once on `right`, probed many times. load_factor < 0 selects the constructor's default (0.5);
+ * otherwise it must lie in (0, 1]. The caller keeps `right`'s memory alive while the object lives. */
+cudf_amd_status cudf_amd_distinct_hash_join_create(const cudf_amd_column_view* right_keys, int32_t num_right, int32_t nulls_equal,
+                                                   double load_factor, void* stream, cudf_amd_distinct_hash_join_t* out);
+void cudf_amd_distinct_hash_join_destroy(cudf_amd_distinct_hash_join_t h);
+/* out_indices = table of two INT32 columns {left_indices, right_indices}; the left indices strictly ascending. */
+cudf_amd_status cudf_amd_distinct_hash_join_inner_join(cudf_amd_distinct_hash_join_t h, const cudf_amd_column_view* left_keys,
+                                                       int32_t num_left, void* stream, cudf_amd_table_t* out_indices);
+/* out_indices = table of ONE INT32 column of num_rows(left) entries: the right row of each left row, or JoinNoMatch (INT32_MIN).
+ * Nothing is read back from the device: the result is valid in stream order. */
+cudf_amd_status cudf_amd_distinct_hash_join_left_join(cudf_amd_distinct_hash_join_t h, const cudf_amd_column_view* left_keys,
+                                                      int32_t num_left, void* stream, cudf_amd_table_t* out_indices);
 
 /* ---- cudf::distinct_indices / distinct / stable_distinct (reference cpp/include/cudf/stream_compaction.hpp) and cudf::distinct_count
  * (reference cpp/include/cudf/reduction/distinct_count.hpp). keep: cudf::duplicate_keep_option (0 ANY, 1 FIRST, 2 LAST, 3 NONE);
