@@ -2,8 +2,14 @@
 """Headline benchmark (BASELINE.json): rows/s of hash-groupby SUM+COUNT over 1B int64-key / float64-value rows
 with 1M groups (configs[1], "C2"), one process per GPU.
 
-  python bench.py --gpus 1 --steps K --warmup W [--dump-outputs DIR]
-  python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus 1 --steps K --warmup W [--dump-outputs DIR] [--full]
+  python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N --steps K --warmup W [--full]
+
+A plain run does what the headline figure needs and no more: it generates the rows, warms up, times the K steps, writes the
+outputs if --dump-outputs is given and prints the line. Everything else the benchmark measures or checks runs only with --full,
+after the timed region, and none of it enters `value`: `result_check`, `hash_table_variant`, `two_value_columns_variant`,
+`secondary` and `cpu_baseline` at N == 1, the second form of the exchange at N > 1, `config.checks` and `cpu_baseline` of a
+--config line.
 
 A step = one pass of the hot path over one batch of synthetic rows already resident in HBM:
   N == 1: cudf::groupby::groupby(keys).aggregate({values, [SUM, COUNT_VALID]}) through the C ABI.
@@ -12,11 +18,11 @@ A step = one pass of the hot path over one batch of synthetic rows already resid
           rows by ncclSend / ncclRecv over xGMI -> per-GPU groupby. It is bound by the point-to-point xGMI links ((N-1)/N of
           16 GB per GPU over N-1 links). The COMBINER form (cudf::distributed::combine_groupby: per-GPU groupby -> exchange of
           the <= 1M partial groups -> merge groupby on the owner; identical result, xGMI carries MBs) is timed in the same run
-          after the primary region and reported beside it as `preaggregated_variant`. BENCH_DIST_MODE=preaggregate swaps
+          after the primary region (--full) and reported beside it as `preaggregated_variant`. BENCH_DIST_MODE=preaggregate swaps
           which of the two is `value`; BENCH_COMBINER=torch runs the combiner through torch.distributed instead of the library.
 Rank 0 prints ONE JSON line. `roofline` is measured live with HIP events on the launch stream (the library's
-per-kernel profiler); `cpu_baseline` times the CPU oracle (oracle/, test infrastructure) on a bounded sample of the
-same workload on this box's host cores, plus pandas/Arrow on configs[0] (10M rows).
+per-kernel profiler) during the timed steps themselves; `cpu_baseline` (--full) times the CPU oracle (oracle/, test
+infrastructure) on a bounded sample of the same workload on the host's cores, plus pandas/Arrow on configs[0] (10M rows).
 """
 import argparse
 import json
@@ -58,9 +64,15 @@ def parse():
                          "range (hash table instead of the direct-address table); c3inrange = dense keys whose misses lie INSIDE the build side's key range "
                          "(no free range reject); c4 = configs[3] multi-key groupby. One GPU only.")
     ap.add_argument("--scale", type=float, default=1.0, help="c3 / c4: fraction of the BASELINE size (parity / smoke runs)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also run everything that the headline figure does not need: the check of the last step's "
+                         "result against a torch reference (`result_check`; `config.checks` of a --config line), the variants and the "
+                         "C3 / C3-sparse / C3-in-range / C4 child runs (`hash_table_variant`, `two_value_columns_variant`, `secondary`), the "
+                         "CPU baselines (`cpu_baseline`) and, at N > 1, the second form of the exchange. Off by default: a plain run "
+                         "sets up, warms up, times the steps, writes --dump-outputs and prints the line.")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave `cpu_baseline` out")
     ap.add_argument("--no-secondary", action="store_true",
-                    help="c2 at one GPU: skip the variants (hash-table keys, two value columns) and the C3 / C3-sparse / C4 runs that the "
+                    help="with --full, c2 at one GPU: skip the variants (hash-table keys, two value columns) and the C3 / C3-sparse / C4 runs that the "
                          "headline line otherwise carries in `hash_table_variant`, `two_value_columns_variant` and `secondary`")
     ap.add_argument("--variant-steps", type=int, default=5)
     ap.add_argument("--cpu-sample-rows", type=int, default=60_000_000)
@@ -170,7 +182,7 @@ def run_config(args, json_fd):
     dt = time.perf_counter() - t0
     _lib.profile_enable(False)
     prof = _lib.profile_report()
-    checks = check(res)
+    checks = check(res) if args.full else None  # (the property checks run a torch reference of the whole configuration)
     nbytes = algo(res)
     ms = dt / args.steps * 1e3
     name, (launches, total_ms) = max(prof.items(), key=lambda kv: kv[1][1])
@@ -204,7 +216,7 @@ def run_config(args, json_fd):
                          "launches_per_step": launches / args.steps, "algorithmic_bytes_per_step": nbytes,
                          "kernels_ms_per_step": {k: v[1] / args.steps for k, v in sorted(prof.items())},
                          "whole_call_frac": nbytes / (ms * 1e-3) / 1e9 / HBM_PEAK_GBS}}
-    if not args.no_cpu_baseline:
+    if args.full and not args.no_cpu_baseline:
         line["cpu_baseline"] = cpu_baseline_config(args.config, rows)
     os.write(json_fd, (json.dumps(line) + "\n").encode())
 
@@ -221,7 +233,7 @@ def run_secondary_children():
                                  ("c3inrange", "c3inrange", {}), ("c4", "c4", {})):
         t0 = time.perf_counter()
         try:
-            p = subprocess.run([sys.executable, os.path.abspath(__file__), "--config", cfg, "--steps", "3", "--warmup", "1", "--no-cpu-baseline"],
+            p = subprocess.run([sys.executable, os.path.abspath(__file__), "--config", cfg, "--steps", "3", "--warmup", "1", "--full", "--no-cpu-baseline"],
                                stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=budget_s, cwd=ROOT, env={**os.environ, **env_extra})
             lines = [ln for ln in p.stdout.decode(errors="replace").splitlines() if ln.startswith("{")]
             if p.returncode != 0 or not lines:
@@ -386,12 +398,12 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
     dt = float(t.item())
 
-    # ---- N == 1, after the timed region: the LAST timed step's result against a per-group torch reference of the same rows
+    # ---- N == 1, --full, after the timed region: the LAST timed step's result against a per-group torch reference of the same rows
     # (bincount / scatter_add_; nothing from oracle/). Keys and counts exactly; sums in units of the reference's own rule
     # |x - y| <= 4 eps |x + y| (cpp/tests/utilities/column_utilities.cu:436-440) and against the worst-case bound of ANY summation
     # order of m values below 1, m^2 eps (both sides add with unordered atomics, as the reference does).
     result_check = None
-    if world == 1 and not force_dist:
+    if args.full and world == 1 and not force_dist:
         try:
             rkeys, rres = last[1]
             k_out = rkeys.columns()[0].to_torch()
@@ -430,14 +442,14 @@ def main():
                                            {"sum": res[0].to_torch(), "count_valid": res[1].to_torch()})
         sys.stderr.write(f"[bench] --dump-outputs: {written} of {groups_out} groups written to {args.dump_outputs}\n")
 
-    # ---- N == 1, after the primary timed region: the other side of the cliffs next to the headline, in the driver's own record.
+    # ---- N == 1, --full, after the primary timed region: the other side of the cliffs next to the headline, in the driver's own record.
     # hash_table_variant: the same rows with every key multiplied by an odd constant (a bijection: same groups, same counts, but
     # the keys no longer span a small range, so the open-addressing hash tables serve the call instead of the direct-address ones);
     # two_value_columns_variant: the same keys with a second float64 column, {a: SUM, COUNT; b: SUM};
     # secondary: BASELINE configs[2] / configs[3] (and the sparse-key form of the join) at full size, each in a CHILD process (its
     # own HIP context: a failure there cannot cost the headline its line), with the property checks of bench_configs.py.
     extras = {}
-    if world == 1 and not force_dist and not args.no_secondary and os.environ.get("BENCH_SECONDARY", "1") != "0":
+    if args.full and world == 1 and not force_dist and not args.no_secondary and os.environ.get("BENCH_SECONDARY", "1") != "0":
         primary_groups = last[1][0].num_rows()
         last = (last[0], None)
 
@@ -553,12 +565,12 @@ def main():
             line["raw_row_shuffle_variant" if other_mode != "preaggregate" else "preaggregated_variant"] = {"error": pre_error}
         if world == 1 and not force_dist:
             line.update(extras)
-        if world == 1 and not force_dist and not args.no_cpu_baseline:
+        if args.full and world == 1 and not force_dist and not args.no_cpu_baseline:
             line["cpu_baseline"] = cpu_baseline(groups, args.cpu_sample_rows)
         return line
 
 
-    # N > 1: also time the other form of the exchange (raw-row shuffle by default); reported next to `value`. The
+    # N > 1, --full: also time the other form of the exchange (raw-row shuffle by default); reported next to `value`. The
     # secondary form must never cost the primary number its JSON line: an exception is reported in the line, and a
     # watchdog prints the line without it if the secondary form has not finished in time (a collective that never
     # returns cannot be interrupted from Python).
@@ -581,7 +593,7 @@ def main():
             os._exit(3)
 
     watchdog_s = int(os.environ.get("BENCH_VARIANT_TIMEOUT_S", "300"))
-    if world > 1 or force_dist:
+    if args.full and (world > 1 or force_dist):
         from cudf_amd import distributed as D2
 
         # the combiner form comes from the library too (cudf::distributed::combine_groupby: local partials -> exchange of the partial
