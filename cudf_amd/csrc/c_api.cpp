@@ -10,6 +10,7 @@
 #include <cudf/groupby.hpp>
 #include <cudf/partitioning.hpp>
 #include <cudf/reduction/distinct_count.hpp>
+#include <cudf/sorting.hpp>
 #include <cudf/stream_compaction.hpp>
 #include <cudf/interop.hpp>
 #include <cudf/join/distinct_hash_join.hpp>
@@ -641,6 +642,74 @@ cudf_amd_status cudf_amd_distinct_count_table(const cudf_amd_column_view* input,
     cudf::stream_ref const s{as_stream(stream)};
     *out_count = cudf::distinct_count(to_table(input, num_columns),
                                       nulls_equal ? cudf::null_equality::EQUAL : cudf::null_equality::UNEQUAL, s);
+  });
+}
+
+// the orders of the sorting calls: int32 arrays with their own lengths, so that a wrong length reaches the C++ check
+static std::vector<cudf::order> orders_of(const int32_t* v, int32_t n)
+{
+  CUDF_EXPECTS(n >= 0 && (n == 0 || v != nullptr), "column_order: a negative length or NULL", std::invalid_argument);
+  std::vector<cudf::order> out;
+  for (int32_t i = 0; i < n; ++i) out.push_back(v[i] ? cudf::order::DESCENDING : cudf::order::ASCENDING);
+  return out;
+}
+static std::vector<cudf::null_order> null_orders_of(const int32_t* v, int32_t n)
+{
+  CUDF_EXPECTS(n >= 0 && (n == 0 || v != nullptr), "null_precedence: a negative length or NULL", std::invalid_argument);
+  std::vector<cudf::null_order> out;
+  for (int32_t i = 0; i < n; ++i) out.push_back(v[i] ? cudf::null_order::BEFORE : cudf::null_order::AFTER);
+  return out;
+}
+
+cudf_amd_status cudf_amd_sorted_order(const cudf_amd_column_view* input, int32_t num_columns, const int32_t* column_order,
+                                      int32_t num_order, const int32_t* null_precedence, int32_t num_precedence, int32_t stable,
+                                      void* stream, cudf_amd_table_t* out_indices)
+{
+  return guarded([&] {
+    *out_indices = nullptr;
+    CUDF_EXPECTS(num_columns >= 0, "num_columns must not be negative", std::invalid_argument);
+    cudf::stream_ref const s{as_stream(stream)};
+    auto const in = to_table(input, num_columns);
+    auto const o  = orders_of(column_order, num_order);
+    auto const np = null_orders_of(null_precedence, num_precedence);
+    auto t        = std::make_unique<cudf_amd_table_s>();
+    t->cols.push_back(stable ? cudf::stable_sorted_order(in, o, np, s) : cudf::sorted_order(in, o, np, s));
+    *out_indices = t.release();
+  });
+}
+
+cudf_amd_status cudf_amd_sort_by_key(const cudf_amd_column_view* values, int32_t num_values, const cudf_amd_column_view* keys,
+                                     int32_t num_keys, const int32_t* column_order, int32_t num_order,
+                                     const int32_t* null_precedence, int32_t num_precedence, int32_t stable, void* stream,
+                                     cudf_amd_table_t* out_table)
+{
+  return guarded([&] {
+    *out_table = nullptr;
+    CUDF_EXPECTS(num_values >= 0 && num_keys >= 0, "num_values and num_keys must not be negative", std::invalid_argument);
+    cudf::stream_ref const s{as_stream(stream)};
+    auto const v  = to_table(values, num_values);
+    auto const k  = to_table(keys, num_keys);
+    auto const o  = orders_of(column_order, num_order);
+    auto const np = null_orders_of(null_precedence, num_precedence);
+    auto tbl      = stable ? cudf::stable_sort_by_key(v, k, o, np, s) : cudf::sort_by_key(v, k, o, np, s);
+    auto t        = std::make_unique<cudf_amd_table_s>();
+    t->cols       = tbl->release();
+    *out_table    = t.release();
+  });
+}
+
+cudf_amd_status cudf_amd_is_sorted(const cudf_amd_column_view* input, int32_t num_columns, const int32_t* column_order,
+                                   int32_t num_order, const int32_t* null_precedence, int32_t num_precedence, void* stream,
+                                   int32_t* out)
+{
+  return guarded([&] {
+    CUDF_EXPECTS(out != nullptr, "out must not be NULL", std::invalid_argument);
+    CUDF_EXPECTS(num_columns >= 0, "num_columns must not be negative", std::invalid_argument);
+    cudf::stream_ref const s{as_stream(stream)};
+    *out = cudf::is_sorted(to_table(input, num_columns), orders_of(column_order, num_order),
+                           null_orders_of(null_precedence, num_precedence), s)
+             ? 1
+             : 0;
   });
 }
 

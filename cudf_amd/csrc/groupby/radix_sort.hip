@@ -3,6 +3,7 @@
 // Nothing here knows of groups; the one place that reads columns is k_fill_words, which makes the words a pass sorts by.
 #include "sort_helper.hpp"
 #include "../common/profiler.hpp"
+#include "../sorting/sorting_impl.hpp"
 
 #include <cudf/utilities/error.hpp>
 
@@ -333,6 +334,13 @@ uint32_t pair_sorter::sort_by(fill_args fa)
     hipLaunchKernelGGL(k_fill_words, dim3(fill_grid(_n)), dim3(256), 0, _s, fa);
   }
   return sort_filled();
+}
+
+void pair_sorter::sort_by_packed(cudf::detail::sorting::plan_word const& w)
+{
+  reset_reduction();
+  cudf::detail::sorting::launch_fill_packed_words(w, payload(), _k[_cur], _or_and, _n, _s);
+  sort_filled();
 }
 
 void pair_sorter::reset_reduction() { hipLaunchKernelGGL(k_init_or_and, dim3(1), dim3(1), 0, _s, _or_and, _ones); }

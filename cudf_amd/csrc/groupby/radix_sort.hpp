@@ -6,6 +6,10 @@
 
 #include <hip/hip_runtime.h>
 
+namespace cudf::detail::sorting {
+struct plan_word;  // sorting/sorting_impl.hpp
+}
+
 namespace cudf::groupby::detail {
 
 // out[0 .. n) = exclusive prefix sums of in[0 .. n); *total (device, optional) = the sum. in == out is allowed.
@@ -47,6 +51,8 @@ class pair_sorter {
   // makes the words of fa's source from the payloads in front and sorts the pairs by them, stably (one synchronisation: the
   // OR / AND of the words comes back to pick the digits that differ); returns the count of WORD_ANY_NULL ones
   uint32_t sort_by(fill_args fa);
+  // as sort_by, by one packed word of several key columns (cudf::sorted_order: sorting/sorting_impl.hpp)
+  void sort_by_packed(cudf::detail::sorting::plan_word const& w);
   // the words in front: those of the last sort_by(), in sorted order
   [[nodiscard]] uint64_t const* words() const { return _k[_cur]; }
   // payload after the last pass, materialised (identity if nothing ever moved)

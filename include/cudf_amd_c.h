@@ -222,6 +222,26 @@ cudf_amd_status cudf_amd_distinct_count_column(const cudf_amd_column_view* input
 cudf_amd_status cudf_amd_distinct_count_table(const cudf_amd_column_view* input, int32_t num_columns, int32_t nulls_equal,
                                               void* stream, int32_t* out_count);
 
+/* ---- cudf::sorted_order / sort / sort_by_key, their stable_ forms and cudf::is_sorted (reference cpp/include/cudf/sorting.hpp).
+ * column_order: cudf::order per key column (0 ASCENDING, 1 DESCENDING), num_order entries; null_precedence: cudf::null_order per
+ * key column (0 AFTER, 1 BEFORE), num_precedence entries. A length of 0 selects the default (ASCENDING / BEFORE for every
+ * column); any other length that differs from the number of key columns returns CUDF_AMD_LOGIC_ERROR.
+ * stable: 0 = the plain call, 1 = its stable_ form.
+ * cudf_amd_sorted_order: out_indices = table of ONE INT32 column of num_rows entries, the row indices in sorted order.
+ * cudf_amd_sort_by_key: every column of `values` gathered in the order of `keys` (cudf::sort is the call with values == keys);
+ * a row-count mismatch between values and keys returns CUDF_AMD_LOGIC_ERROR.
+ * cudf_amd_is_sorted: *out = 1 if no row is lexicographically less than its predecessor, else 0. */
+cudf_amd_status cudf_amd_sorted_order(const cudf_amd_column_view* input, int32_t num_columns, const int32_t* column_order,
+                                      int32_t num_order, const int32_t* null_precedence, int32_t num_precedence, int32_t stable,
+                                      void* stream, cudf_amd_table_t* out_indices);
+cudf_amd_status cudf_amd_sort_by_key(const cudf_amd_column_view* values, int32_t num_values, const cudf_amd_column_view* keys,
+                                     int32_t num_keys, const int32_t* column_order, int32_t num_order,
+                                     const int32_t* null_precedence, int32_t num_precedence, int32_t stable, void* stream,
+                                     cudf_amd_table_t* out_table);
+cudf_amd_status cudf_amd_is_sorted(const cudf_amd_column_view* input, int32_t num_columns, const int32_t* column_order,
+                                   int32_t num_order, const int32_t* null_precedence, int32_t num_precedence, void* stream,
+                                   int32_t* out);
+
 /* ---- Arrow C Data Interface (reference cpp/include/cudf/interop.hpp: from_arrow :685-689, to_arrow_host :618-621,
  * to_arrow_schema :473-475). The structs are the ones the Arrow specification publishes.
  * cudf_amd_from_arrow: host Arrow struct array (one child per column) -> owning device table; the input is not
