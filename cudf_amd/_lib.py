@@ -49,6 +49,7 @@ SYMBOLS = {
     "cudf_amd_profile_enable": (C.c_int, [C.c_int32]),
     "cudf_amd_profile_reset": (C.c_int, []),
     "cudf_amd_profile_report": (C.c_int, [C.c_char_p, C.c_size_t]),
+    "cudf_amd_profile_variants": (C.c_int, [C.c_char_p, C.c_size_t]),
     "cudf_amd_table_num_columns": (C.c_int32, [_P]),
     "cudf_amd_table_num_rows": (C.c_int32, [_P]),
     "cudf_amd_table_column": (C.c_int, [_P, C.c_int32, C.POINTER(ColumnView)]),
@@ -179,4 +180,16 @@ def profile_report():
     for line in buf.value.decode().splitlines():
         name, n, ms = line.split()
         out[name] = (int(n), float(ms))
+    return out
+
+
+def profile_variants():
+    """{(family, label): launches since the last reset} for every kernel instantiation the library registers, launched or not
+    (launches are counted while profiling is enabled). Needs no GPU."""
+    buf = C.create_string_buffer(1 << 18)
+    check(load().cudf_amd_profile_variants(buf, len(buf)))
+    out = {}
+    for line in buf.value.decode().splitlines():
+        family, label, n = line.split()
+        out[(family, label)] = int(n)
     return out

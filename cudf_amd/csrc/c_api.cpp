@@ -231,6 +231,16 @@ cudf_amd_status cudf_amd_profile_report(char* buf, size_t n)
     }
   });
 }
+cudf_amd_status cudf_amd_profile_variants(char* buf, size_t n)
+{
+  return guarded([&] {
+    std::string out;
+    for (auto const& v : cudf::detail::prof::variants()) out += v.family + " " + v.label + " " + std::to_string(v.launches) + "\n";
+    CUDF_EXPECTS(buf != nullptr && out.size() < n,
+                 "cudf_amd_profile_variants: the buffer is too small (" + std::to_string(out.size() + 1) + " bytes needed)", std::invalid_argument);
+    std::memcpy(buf, out.c_str(), out.size() + 1);
+  });
+}
 
 int32_t cudf_amd_table_num_columns(cudf_amd_table_t t) { return t ? static_cast<int32_t>(t->cols.size()) : 0; }
 int32_t cudf_amd_table_num_rows(cudf_amd_table_t t) { return (t && !t->cols.empty()) ? t->cols.front()->size() : 0; }

@@ -630,6 +630,19 @@ __global__ void __launch_bounds__(1024, 4) k_aggregate(agg_args const* __restric
 
 }  // namespace
 
+// one k_aggregate instantiation, spelled out for the variant registry (common/profiler.hpp)
+template <int INPUT, int KUT, int PAYT, int NACCT, bool SIMPLE, bool EXACT, uint64_t SIG>
+struct aggregate_variant {
+  static char const* family() { return "aggregate"; }
+  static std::string label()
+  {
+    return cudf::detail::prof::variant_label(
+      "aggregate", {INPUT == IN_COLUMNS ? "columns" : (INPUT == IN_RAW_RECORDS ? "raw" : "partial"), "ku" + std::to_string(KUT),
+                    "pay" + std::to_string(PAYT), "acc" + std::to_string(NACCT), SIMPLE ? "plain" : "generic", EXACT ? "exact" : "anywidth",
+                    sig_label(SIG)});
+  }
+};
+
 template <int INPUT, int KUT, int PAYT, int NACCT, bool SIMPLE, bool EXACT, uint64_t SIG = 0>
 static void launch_aggregate_n(agg_args const& a, agg_args* d_args, hipStream_t stream)
 {
@@ -638,6 +651,7 @@ static void launch_aggregate_n(agg_args const& a, agg_args* d_args, hipStream_t 
   std::call_once(attr_once, [] { allow_full_lds(reinterpret_cast<void const*>(&k_aggregate<INPUT, KUT, PAYT, NACCT, SIMPLE, EXACT, SIG>)); });
   hipLaunchKernelGGL(k_store_args<agg_args>, dim3(1), dim3(1), 0, stream, a, d_args);
   cudf::detail::prof::scope prof_{"aggregate", stream};
+  cudf::detail::prof::count_variant(cudf::detail::prof::variant<aggregate_variant<INPUT, KUT, PAYT, NACCT, SIMPLE, EXACT, SIG>>::slot);
   hipLaunchKernelGGL((k_aggregate<INPUT, KUT, PAYT, NACCT, SIMPLE, EXACT, SIG>), dim3(a.nitems), dim3(a.geom.block), lds,
                      stream, d_args);
   CUDF_HIP_TRY(hipGetLastError());
@@ -647,9 +661,18 @@ static void launch_aggregate_n(agg_args const& a, agg_args* d_args, hipStream_t 
 template <int INPUT, int KUT, int PAYT, bool SIMPLE, bool EXACT>
 static void launch_aggregate_t(agg_args const& a, agg_args* d_args, hipStream_t stream)
 {
-  if (a.plan.NACC <= 2) return launch_aggregate_n<INPUT, KUT, PAYT, 2, SIMPLE, EXACT>(a, d_args, stream);
-  if (a.plan.NACC <= 4) return launch_aggregate_n<INPUT, KUT, PAYT, 4, SIMPLE, EXACT>(a, d_args, stream);
-  return launch_aggregate_n<INPUT, KUT, PAYT, MAX_ACC, SIMPLE, EXACT>(a, d_args, stream);
+  // The payload units of a PARTIAL record are its accumulators (launch_aggregate_records: npay == NACC). An exact shape has one
+  // bucket, and one key unit with at most two accumulators is always an exact shape: the other buckets would be instantiations
+  // that no call can reach (tests/groupby_variants.py checks that every compiled one is reached).
+  if constexpr (INPUT == IN_PARTIAL_RECORDS && EXACT) {
+    return launch_aggregate_n<INPUT, KUT, PAYT, (PAYT <= 2 ? 2 : (PAYT <= 4 ? 4 : MAX_ACC)), SIMPLE, EXACT>(a, d_args, stream);
+  } else {
+    if constexpr (!(INPUT == IN_PARTIAL_RECORDS && KUT == 1)) {
+      if (a.plan.NACC <= 2) return launch_aggregate_n<INPUT, KUT, PAYT, 2, SIMPLE, EXACT>(a, d_args, stream);
+    }
+    if (a.plan.NACC <= 4) return launch_aggregate_n<INPUT, KUT, PAYT, 4, SIMPLE, EXACT>(a, d_args, stream);
+    return launch_aggregate_n<INPUT, KUT, PAYT, MAX_ACC, SIMPLE, EXACT>(a, d_args, stream);
+  }
 }
 
 

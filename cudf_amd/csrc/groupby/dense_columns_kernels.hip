@@ -206,12 +206,23 @@ __global__ void __launch_bounds__(1024) k_aggregate_dense_columns(dense_agg_args
     gstore(reinterpret_cast<u64x2*>(image) + i, reinterpret_cast<u64x2 const*>(lds_raw)[i]);
 }
 
+// one k_aggregate_dense_columns instantiation, spelled out for the variant registry (common/profiler.hpp)
+template <uint64_t SIG, int NACCT, int SRC, int NV>
+struct dcol_variant {
+  static char const* family() { return "dense_aggregate"; }
+  static std::string label()
+  {
+    return cudf::detail::prof::variant_label("dense_columns", {sig_label(SIG), "acc" + std::to_string(NACCT), SRC == DCOL_SIMPLE ? "simple" : "cols",
+                                                               "nv" + std::to_string(NV)});
+  }
+};
 template <uint64_t SIG, int NACCT, int SRC, int NV = 1>
 void launch_dcol_t(dense_agg_args const& a, dense_agg_args const* d_args, hipStream_t stream)
 {
   static std::once_flag attr_once;  // (the API is re-entrant across objects: two threads may launch this kernel first)
   std::call_once(attr_once, [] { allow_full_lds(reinterpret_cast<void const*>(&k_aggregate_dense_columns<SIG, NACCT, SRC, NV>)); });
   cudf::detail::prof::scope prof_{"aggregate", stream};
+  cudf::detail::prof::count_variant(cudf::detail::prof::variant<dcol_variant<SIG, NACCT, SRC, NV>>::slot);
   hipLaunchKernelGGL((k_aggregate_dense_columns<SIG, NACCT, SRC, NV>), dim3(a.nsplit), dim3(1024), a.image_bytes, stream, d_args);
   CUDF_HIP_TRY(hipGetLastError());
 }

@@ -503,12 +503,22 @@ void store_args(dense_agg_args const& a, dense_agg_args* d_args, hipStream_t str
   CUDF_HIP_TRY(hipGetLastError());
 }
 
+// one k_aggregate_dense instantiation, spelled out for the variant registry (common/profiler.hpp)
+template <uint64_t SIG, int NACCT, bool SOA>
+struct dense_variant {
+  static char const* family() { return "dense_aggregate"; }
+  static std::string label()
+  {
+    return cudf::detail::prof::variant_label("dense_aggregate", {sig_label(SIG), "acc" + std::to_string(NACCT), SOA ? "streams" : "records"});
+  }
+};
 template <uint64_t SIG, int NACCT, bool SOA>
 static void launch_dense_t(dense_agg_args const& a, dense_agg_args const* d_args, hipStream_t stream)
 {
   static std::once_flag attr_once;  // (the API is re-entrant across objects: two threads may launch this kernel first)
   std::call_once(attr_once, [] { allow_full_lds(reinterpret_cast<void const*>(&k_aggregate_dense<SIG, NACCT, SOA>)); });
   cudf::detail::prof::scope prof_{"aggregate", stream};
+  cudf::detail::prof::count_variant(cudf::detail::prof::variant<dense_variant<SIG, NACCT, SOA>>::slot);
   hipLaunchKernelGGL((k_aggregate_dense<SIG, NACCT, SOA>), dim3(a.nitems * std::max(a.nsplit, 1)), dim3(a.block), a.image_bytes, stream, d_args);
   CUDF_HIP_TRY(hipGetLastError());
 }

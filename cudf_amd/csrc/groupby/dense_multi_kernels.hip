@@ -208,6 +208,16 @@ __global__ void __launch_bounds__(1024) k_dense_merge_dump_multi(dense_multi_mer
   if (threadIdx.x == 0) a.out_count[blockIdx.x] = static_cast<int32_t>(s_dump);
 }
 
+// one k_dense_ring_scatter_multi instantiation, spelled out for the variant registry (common/profiler.hpp)
+template <int NV, bool DENSE, int CAP, int RPT, int D>
+struct ring_multi_variant {
+  static char const* family() { return "ring_scatter_multi"; }
+  static std::string label()
+  {
+    return cudf::detail::prof::variant_label("ring_scatter_multi", {"nv" + std::to_string(NV), DENSE ? "dense" : "hash", "cap" + std::to_string(CAP),
+                                                                    "rpt" + std::to_string(RPT), "d" + std::to_string(D)});
+  }
+};
 template <int NV, bool DENSE, int CAP, int RPT, int D>
 void launch_multi_t(ring_multi_args const& a, ring_multi_args const* d_args, hipStream_t stream)
 {
@@ -216,6 +226,7 @@ void launch_multi_t(ring_multi_args const& a, ring_multi_args const* d_args, hip
   static_assert(DENSE, "the sparse-key (hash) form of this scatter was measured slower and removed (profiles/r3_sparse_ring.txt)");
   std::size_t const lds = dense_ring_multi_lds_bytes(NV, a.P, CAP);
   cudf::detail::prof::scope prof_{"partition_scatter", stream};
+  cudf::detail::prof::count_variant(cudf::detail::prof::variant<ring_multi_variant<NV, DENSE, CAP, RPT, D>>::slot);
   hipLaunchKernelGGL((k_dense_ring_scatter_multi<NV, DENSE, CAP, RPT, D>), dim3(a.slices), dim3(1024), lds, stream, d_args);
   CUDF_HIP_TRY(hipGetLastError());
 }

@@ -317,6 +317,30 @@ __global__ void __launch_bounds__(1024) k_dense_ring_scatter(dense_ring_args con
   }
 }
 
+// one k_dense_ring_scatter instantiation, spelled out for the variant registry (common/profiler.hpp); a static column shape reads
+// k<key width>[m] per key column and v[m] for the value, m = the column carries a validity mask
+template <typename SHAPE>
+std::string shape_label()
+{
+  if constexpr (std::is_void_v<SHAPE>) {
+    return "-";
+  } else {
+    std::string out = "k" + std::to_string(SHAPE::W0) + (SHAPE::M0 ? "m" : "");
+    if (SHAPE::W1 != 0) out += ".k" + std::to_string(SHAPE::W1) + (SHAPE::M1 ? "m" : "");
+    return out + (SHAPE::MV ? ".vm" : ".v");
+  }
+}
+template <int SRC, int RPT, int D, typename TAG, bool HOT, typename SHAPE>
+struct ring_variant {
+  static char const* family() { return "ring_scatter"; }
+  static std::string label()
+  {
+    static char const* const srcs[] = {"simple", "cols", "regions", "static"};
+    return cudf::detail::prof::variant_label("ring_scatter", {srcs[SRC], "rpt" + std::to_string(RPT), "d" + std::to_string(D),
+                                                              "tag" + std::to_string(8 * sizeof(TAG)), HOT ? "hot" : "nohot", shape_label<SHAPE>()});
+  }
+};
+
 template <int SRC, int RPT, int D, typename TAG, bool HOT = false, typename SHAPE = void>
 void launch_ring_tag(dense_ring_args const& a, dense_ring_args const* d_args, hipStream_t stream)
 {
@@ -326,6 +350,7 @@ void launch_ring_tag(dense_ring_args const& a, dense_ring_args const* d_args, hi
   std::size_t const lds = static_cast<std::size_t>(DENSE_RING_SLOTS) * 16 + 2048 + (HOT ? static_cast<std::size_t>(HOT_SLOTS) * (8 + 8 + 4) : 0);
   int const items       = a.from_columns ? a.slices : a.nseg * a.slices;
   cudf::detail::prof::scope prof_{a.from_columns ? "partition_scatter" : "partition_scatter_level2", stream};
+  cudf::detail::prof::count_variant(cudf::detail::prof::variant<ring_variant<SRC, RPT, D, TAG, HOT, SHAPE>>::slot);
   hipLaunchKernelGGL((k_dense_ring_scatter<SRC, RPT, D, TAG, HOT, SHAPE>), dim3(items), dim3(1024), lds, stream, d_args);
   CUDF_HIP_TRY(hipGetLastError());
 }

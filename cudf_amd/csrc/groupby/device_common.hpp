@@ -159,6 +159,19 @@ inline uint64_t plan_sig(plan_dev const& p)
   }
   return make_sig(p.NACC, a[0], a[1], a[2], a[3]);
 }
+// A signature spelled out for a variant label (common/profiler.hpp): "rt" for 0, else one field per accumulator joined by '+',
+// op.src.pay.vbit with '-' for "none" - SIG_SUMF_CNT is "addf.value.p0.v-+addi.one.p-.v-".
+inline std::string sig_label(uint64_t s)
+{
+  static char const* const ops[]  = {"addi", "addf", "mini", "minu", "minf", "maxi", "maxu", "maxf", "muli", "mulf", "any"};
+  static char const* const srcs[] = {"value", "one_if_valid", "one", "square"};
+  if (s == 0) return "rt";
+  auto idx = [](int v) { return v < 0 ? std::string{"-"} : std::to_string(v); };
+  std::string out;
+  for (int q = 0; q < sig_n(s); ++q)
+    out += std::string(q ? "+" : "") + ops[sig_op(s, q)] + "." + srcs[sig_src(s, q)] + ".p" + idx(sig_pay(s, q)) + ".v" + idx(sig_vbit(s, q));
+  return out;
+}
 // hot signatures with their own instantiation
 constexpr uint64_t SIG_SUMF_CNT = make_sig(2, sig_acc(ADD_F64, SRC_VALUE, 0, -1), sig_acc(ADD_I64, SRC_ONE, -1, -1));
 constexpr uint64_t SIG_SUMI_CNT = make_sig(2, sig_acc(ADD_I64, SRC_VALUE, 0, -1), sig_acc(ADD_I64, SRC_ONE, -1, -1));

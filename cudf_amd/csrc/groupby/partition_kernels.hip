@@ -510,15 +510,48 @@ void store_args(part_args const& a, part_args* d_args, hipStream_t stream)
   CUDF_HIP_TRY(hipGetLastError());
 }
 
-void launch_partition_hist(part_args const& a, part_args const* d_args, hipStream_t stream)
+// the partition kernels' instantiations, spelled out for the variant registry (common/profiler.hpp)
+using cudf::detail::prof::count_variant;
+using cudf::detail::prof::variant;
+using cudf::detail::prof::variant_label;
+template <bool SIMPLE>
+struct hist_variant {
+  static char const* family() { return "partition"; }
+  static std::string label() { return variant_label("partition_hist", {SIMPLE ? "plain" : "generic"}); }
+};
+template <int UT, int RPT, bool SIMPLE, bool EXACT>
+struct scatter_variant {
+  static char const* family() { return "partition"; }
+  static std::string label()
+  {
+    return variant_label("partition_scatter", {"ut" + std::to_string(UT), "rpt" + std::to_string(RPT), SIMPLE ? "plain" : "generic", EXACT ? "exact" : "anywidth"});
+  }
+};
+template <int UT, int RPT, int G, int SRC, bool HOT, bool DENSE>
+struct wc_scatter_variant {
+  static char const* family() { return "wc_scatter"; }
+  static std::string label()
+  {
+    static char const* const srcs[] = {"simple", "columns", "records", "dense_cols"};
+    static_assert(WC_SRC_SIMPLE == 0 && WC_SRC_COLUMNS == 1 && WC_SRC_RECORDS == 2 && WC_SRC_DENSE_COLS == 3, "wc_scatter_variant: source names");
+    return variant_label("wc_scatter", {"ut" + std::to_string(UT), "rpt" + std::to_string(RPT), "g" + std::to_string(G), srcs[SRC], HOT ? "hot" : "nohot",
+                                        DENSE ? "dense" : "hash"});
+  }
+};
+
+template <bool SIMPLE>
+static void launch_hist_t(part_args const& a, part_args const* d_args, hipStream_t stream)
 {
   int const items = a.geom.nseg * a.geom.slices;
   cudf::detail::prof::scope prof_{"partition_hist", stream};
-  if (a.plan.simple && a.from_columns)
-    hipLaunchKernelGGL(k_partition_hist<true>, dim3(items), dim3(a.geom.block), a.geom.P * sizeof(uint32_t), stream, d_args);
-  else
-    hipLaunchKernelGGL(k_partition_hist<false>, dim3(items), dim3(a.geom.block), a.geom.P * sizeof(uint32_t), stream, d_args);
+  count_variant(variant<hist_variant<SIMPLE>>::slot);
+  hipLaunchKernelGGL(k_partition_hist<SIMPLE>, dim3(items), dim3(a.geom.block), a.geom.P * sizeof(uint32_t), stream, d_args);
   CUDF_HIP_TRY(hipGetLastError());
+}
+void launch_partition_hist(part_args const& a, part_args const* d_args, hipStream_t stream)
+{
+  if (a.plan.simple && a.from_columns) launch_hist_t<true>(a, d_args, stream);
+  else launch_hist_t<false>(a, d_args, stream);
 }
 
 void launch_partition_scan(part_args const& a, part_args const* d_args, hipStream_t stream)
@@ -539,6 +572,7 @@ static void launch_scatter_t(part_args const& a, part_args const* d_args, hipStr
   std::call_once(attr_once, [] { allow_full_lds(reinterpret_cast<void const*>(&k_partition_scatter<UT, RPT, SIMPLE, EXACT>)); });
   int const items = g.nseg * g.slices;
   cudf::detail::prof::scope prof_{"partition_scatter", stream};
+  count_variant(variant<scatter_variant<UT, RPT, SIMPLE, EXACT>>::slot);
   hipLaunchKernelGGL((k_partition_scatter<UT, RPT, SIMPLE, EXACT>), dim3(items), dim3(g.block), lds, stream, d_args);
   CUDF_HIP_TRY(hipGetLastError());
 }
@@ -568,6 +602,7 @@ static void launch_scatter_wc_src(part_args const& a, part_args const* d_args, h
   static std::once_flag attr_once;  // (the API is re-entrant across objects: two threads may launch this kernel first)
   std::call_once(attr_once, [] { allow_full_lds(reinterpret_cast<void const*>(&k_partition_scatter_wc<UT, RPT, G, SRC, HOT, DENSE>)); });
   cudf::detail::prof::scope prof_{a.from_columns ? "partition_scatter" : "partition_scatter_level2", stream};
+  count_variant(variant<wc_scatter_variant<UT, RPT, G, SRC, HOT, DENSE>>::slot);
   hipLaunchKernelGGL((k_partition_scatter_wc<UT, RPT, G, SRC, HOT, DENSE>), dim3(g.nseg * g.slices), dim3(g.block), lds, stream, d_args);
   CUDF_HIP_TRY(hipGetLastError());
 }

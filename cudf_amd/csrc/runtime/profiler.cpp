@@ -4,6 +4,7 @@
 #include <dlfcn.h>
 
 #include <atomic>
+#include <deque>
 #include <map>
 #include <mutex>
 
@@ -17,6 +18,23 @@ std::mutex g_mu;
 bool g_on = false;
 std::vector<pending> g_pending;
 std::map<std::string, std::pair<int64_t, double>> g_totals;
+
+// The variants register from the static initialisers of other translation units, in no particular order relative to this one's:
+// the container is constructed on first use. A deque never moves its elements, so a slot's counter stays where it is.
+struct variant_entry {
+  std::string family, label;
+  std::atomic<int64_t> launches{0};
+  variant_entry(char const* f, std::string l) : family{f}, label{std::move(l)} {}
+};
+struct variant_registry {
+  std::mutex mu;
+  std::deque<variant_entry> entries;
+};
+variant_registry& registry()
+{
+  static variant_registry* const r = new variant_registry;  // (never destroyed: launchers may run during process exit)
+  return *r;
+}
 
 void drain_locked()
 {
@@ -45,6 +63,30 @@ void reset()
   std::lock_guard<std::mutex> g{g_mu};
   drain_locked();
   g_totals.clear();
+  auto& r = registry();
+  std::lock_guard<std::mutex> gr{r.mu};
+  for (auto& e : r.entries) e.launches.store(0, std::memory_order_relaxed);
+}
+
+int register_variant(char const* family, std::string label)
+{
+  auto& r = registry();
+  std::lock_guard<std::mutex> g{r.mu};
+  r.entries.emplace_back(family, std::move(label));
+  return static_cast<int>(r.entries.size()) - 1;
+}
+void count_variant(int slot)
+{
+  if (!g_on) return;
+  registry().entries[static_cast<std::size_t>(slot)].launches.fetch_add(1, std::memory_order_relaxed);
+}
+std::vector<variant_stat> variants()
+{
+  auto& r = registry();
+  std::lock_guard<std::mutex> g{r.mu};
+  std::vector<variant_stat> out;
+  for (auto const& e : r.entries) out.push_back({e.family, e.label, e.launches.load(std::memory_order_relaxed)});
+  return out;
 }
 std::vector<kernel_stat> collect()
 {

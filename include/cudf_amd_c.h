@@ -98,6 +98,10 @@ cudf_amd_status cudf_amd_memory_stats(uint64_t* current_bytes, uint64_t* peak_by
 cudf_amd_status cudf_amd_profile_enable(int32_t on);
 cudf_amd_status cudf_amd_profile_reset(void);
 cudf_amd_status cudf_amd_profile_report(char* buf, size_t n);
+/* One line "family label launches\n" per compiled kernel instantiation that registers itself (the hash-groupby aggregate, partition and
+ * ring-scatter kernels), launched since the last reset or not; launches are counted while profiling is enabled. Needs no device.
+ * CUDF_AMD_INVALID_ARGUMENT if the text and its terminator do not fit n bytes (the message names the size needed). */
+cudf_amd_status cudf_amd_profile_variants(char* buf, size_t n);
 
 /* ---- owning tables */
 int32_t cudf_amd_table_num_columns(cudf_amd_table_t t);

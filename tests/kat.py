@@ -153,6 +153,31 @@ def compare_columns(actual, expected, what="", atol=0.0):
         assert equivalent(a, e, is_float, atol), f"{what}: values differ\n{a}\n{e}"
 
 
+def check_groupby_against_oracle(G, O, keys, requests, include=False, expect_path=None, after_call=None):
+    """One hash-groupby call on the backend `G` against the oracle `O`: keys, integers, counts, MIN / MAX and ARGMIN / ARGMAX exactly;
+    float SUM / MEAN / SUM_OF_SQUARES within sum_atol of the largest group. `after_call` runs between the call and the comparison."""
+    got = sort_groups(*G.groupby(keys, requests, include_null_keys=include))
+    if after_call is not None:
+        after_call()
+    if expect_path is not None:
+        # dense integer keys may take the direct-address tables (DENSE_DIRECT) wherever the partitioned path is expected
+        ok = (expect_path, "DENSE_DIRECT") if expect_path == "PARTITIONED_LDS" else (expect_path,)
+        assert G.last_path.name in ok, G.last_path
+    exp = sort_groups(*O.groupby(keys, requests, include_null_keys=include))
+    assert len(got[0]) == len(exp[0])
+    for a, e in zip(got[0], exp[0]):
+        compare_columns(a, e, "keys")
+    # order-dependent float sums: worst-case bound for the largest group (see sum_atol)
+    cnt = O.groupby(keys, [(requests[0][0], ["count_all"])], include_null_keys=include)[1][0][0][0]
+    m = int(cnt.max()) if len(cnt) else 1
+    for (vals, kinds), ra, re_ in zip(requests, got[1], exp[1]):
+        h = G.to_host_column(vals)
+        scale = float(np.max(np.abs(h.data.astype(np.float64)))) if h.size else 0.0
+        for kind, a, e in zip(kinds, ra, re_):
+            is_fsum = kind in ("sum", "mean", "sum_of_squares") and np.dtype(h.data.dtype).kind == "f"
+            compare_columns(a, e, f"result[{kind}]", atol=sum_atol(m, scale) if is_fsum else 0.0)
+
+
 def groupby_cases():
     doc = load("kat_groupby.json")
     for c in doc["cases"]:

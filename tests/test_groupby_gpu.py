@@ -51,25 +51,7 @@ def test_groupby_errors(G):
         G.groupby([K], [(HostColumn(np.arange(3, dtype=np.int64), None, "timestamp_s"), ["median"])])
 
 
-def _check_against_oracle(G, O, keys, requests, include=False, expect_path=None):
-    got = kat.sort_groups(*G.groupby(keys, requests, include_null_keys=include))
-    if expect_path is not None:
-        # dense integer keys may take the direct-address tables (DENSE_DIRECT) wherever the partitioned path is expected
-        ok = (expect_path, "DENSE_DIRECT") if expect_path == "PARTITIONED_LDS" else (expect_path,)
-        assert G.last_path.name in ok, G.last_path
-    exp = kat.sort_groups(*O.groupby(keys, requests, include_null_keys=include))
-    assert len(got[0]) == len(exp[0])
-    for a, e in zip(got[0], exp[0]):
-        kat.compare_columns(a, e, "keys")
-    # order-dependent float sums: worst-case bound for the largest group (see kat.sum_atol)
-    cnt = O.groupby(keys, [(requests[0][0], ["count_all"])], include_null_keys=include)[1][0][0][0]
-    m = int(cnt.max()) if len(cnt) else 1
-    for (vals, kinds), ra, re_ in zip(requests, got[1], exp[1]):
-        h = G.to_host_column(vals)
-        scale = float(np.max(np.abs(h.data.astype(np.float64)))) if h.size else 0.0
-        for kind, a, e in zip(kinds, ra, re_):
-            is_fsum = kind in ("sum", "mean", "sum_of_squares") and np.dtype(h.data.dtype).kind == "f"
-            kat.compare_columns(a, e, f"result[{kind}]", atol=kat.sum_atol(m, scale) if is_fsum else 0.0)
+_check_against_oracle = kat.check_groupby_against_oracle
 
 
 ALL_AGGS = ["sum", "count_valid", "count_all", "min", "max", "mean"]
