@@ -3,7 +3,8 @@
 Python layer = a pylibcudf-shaped host mirror (Column, Table, groupby.GroupBy, join.inner_join, ...) over the
 C ABI of cudf_amd/lib/libcudf_amd.so. The shared library is the product; importing this package without it
 fails (no CPU fallback)."""
-from . import _lib, aggregation, groupby, join, partitioning, reduce, sorting, stream_compaction, types  # noqa: F401
+from . import (_lib, aggregation, groupby, join, merge, partitioning, reduce, search, sorting, stream_compaction,  # noqa: F401
+               types)
 from .column import Column, Table  # noqa: F401
 from .types import (DataType, DuplicateKeepOption, NanEquality, NanPolicy, NullEquality, NullOrder, NullPolicy, Order,  # noqa: F401
                     Sorted, TypeId)

@@ -97,6 +97,10 @@ SYMBOLS = {
                                        C.c_int32, C.POINTER(C.c_int32), C.c_int32, C.c_int32, _P, C.POINTER(_P)]),
     "cudf_amd_is_sorted": (C.c_int, [C.POINTER(ColumnView), C.c_int32, C.POINTER(C.c_int32), C.c_int32, C.POINTER(C.c_int32),
                                      C.c_int32, _P, C.POINTER(C.c_int32)]),
+    "cudf_amd_search_bound": (C.c_int, [C.POINTER(ColumnView), C.c_int32, C.POINTER(ColumnView), C.c_int32, C.POINTER(C.c_int32),
+                                        C.c_int32, C.POINTER(C.c_int32), C.c_int32, C.c_int32, _P, C.POINTER(_P)]),
+    "cudf_amd_merge": (C.c_int, [C.POINTER(C.POINTER(ColumnView)), C.c_int32, C.c_int32, C.POINTER(C.c_int32), C.c_int32,
+                                 C.POINTER(C.c_int32), C.c_int32, C.POINTER(C.c_int32), C.c_int32, _P, C.POINTER(_P)]),
     "cudf_amd_hash_partition": (C.c_int, [C.POINTER(ColumnView), C.c_int32, C.POINTER(C.c_int32), C.c_int32, C.c_int32,
                                           C.c_uint32, _P, C.POINTER(_P), C.POINTER(C.c_int32)]),
     "cudf_amd_comm_unique_id": (C.c_int, [C.POINTER(C.c_uint8)]),

@@ -10,6 +10,8 @@
 #include <cudf/groupby.hpp>
 #include <cudf/partitioning.hpp>
 #include <cudf/reduction/distinct_count.hpp>
+#include <cudf/merge.hpp>
+#include <cudf/search.hpp>
 #include <cudf/sorting.hpp>
 #include <cudf/stream_compaction.hpp>
 #include <cudf/interop.hpp>
@@ -720,6 +722,46 @@ cudf_amd_status cudf_amd_is_sorted(const cudf_amd_column_view* input, int32_t nu
                            null_orders_of(null_precedence, num_precedence), s)
              ? 1
              : 0;
+  });
+}
+
+cudf_amd_status cudf_amd_search_bound(const cudf_amd_column_view* haystack, int32_t num_columns, const cudf_amd_column_view* needles,
+                                      int32_t num_needle_columns, const int32_t* column_order, int32_t num_order,
+                                      const int32_t* null_precedence, int32_t num_precedence, int32_t upper, void* stream,
+                                      cudf_amd_table_t* out)
+{
+  return guarded([&] {
+    *out = nullptr;
+    CUDF_EXPECTS(num_columns >= 0 && num_needle_columns >= 0, "the numbers of columns must not be negative", std::invalid_argument);
+    cudf::stream_ref const s{as_stream(stream)};
+    auto const h  = to_table(haystack, num_columns);
+    auto const n  = to_table(needles, num_needle_columns);
+    auto const o  = orders_of(column_order, num_order);
+    auto const np = null_orders_of(null_precedence, num_precedence);
+    auto t        = std::make_unique<cudf_amd_table_s>();
+    t->cols.push_back(upper ? cudf::upper_bound(h, n, o, np, s) : cudf::lower_bound(h, n, o, np, s));
+    *out = t.release();
+  });
+}
+
+cudf_amd_status cudf_amd_merge(const cudf_amd_column_view* const* tables, int32_t num_tables, int32_t num_columns,
+                               const int32_t* key_cols, int32_t num_keys, const int32_t* column_order, int32_t num_order,
+                               const int32_t* null_precedence, int32_t num_precedence, void* stream, cudf_amd_table_t* out)
+{
+  return guarded([&] {
+    *out = nullptr;
+    CUDF_EXPECTS(num_tables >= 0 && num_columns >= 0 && num_keys >= 0, "the numbers of tables, columns and keys must not be negative",
+                 std::invalid_argument);
+    CUDF_EXPECTS(num_tables == 0 || tables != nullptr, "tables must not be NULL", std::invalid_argument);
+    CUDF_EXPECTS(num_keys == 0 || key_cols != nullptr, "key_cols must not be NULL", std::invalid_argument);
+    cudf::stream_ref const s{as_stream(stream)};
+    std::vector<cudf::table_view> in;
+    for (int32_t i = 0; i < num_tables; ++i) in.push_back(to_table(tables[i], num_columns));
+    auto tbl   = cudf::merge(in, std::vector<cudf::size_type>(key_cols, key_cols + num_keys), orders_of(column_order, num_order),
+                             null_orders_of(null_precedence, num_precedence), s);
+    auto t     = std::make_unique<cudf_amd_table_s>();
+    t->cols    = tbl->release();
+    *out       = t.release();
   });
 }
 

@@ -14,8 +14,6 @@
 namespace cudf {
 namespace detail {
 namespace sorting {
-namespace {
-
 // The sizes are checked before the trivial cases, so a wrong length is an error for an empty table too.
 void check_orders(table_view const& keys, std::vector<order> const& column_order, std::vector<null_order> const& null_precedence)
 {
@@ -25,8 +23,9 @@ void check_orders(table_view const& keys, std::vector<order> const& column_order
                "Mismatch between number of columns and null_precedence size.");
 }
 
-// The words of `keys`, least significant first (sorting_impl.hpp, "Layout").
-packed_plan make_plan(table_view const& keys, std::vector<order> const& column_order, std::vector<null_order> const& null_precedence)
+// The words of `keys`, least significant first (sorting_impl.hpp, "Layout"); a forced null bit keeps the column's mask nullptr.
+packed_plan make_plan(table_view const& keys, std::vector<order> const& column_order, std::vector<null_order> const& null_precedence,
+                      uint32_t force_null_bit)
 {
   device_table const d = make_device_table(keys);  // (throws beyond MAX_COLS or for a column that is not fixed-width)
   packed_plan p{};
@@ -40,7 +39,7 @@ packed_plan make_plan(table_view const& keys, std::vector<order> const& column_o
     bool const descending = !column_order.empty() && column_order[c] == order::DESCENDING;
     bool const before     = null_precedence.empty() || null_precedence[c] == null_order::BEFORE;
     int const vbits       = d.col[c].cls == CLS_BOOL ? 1 : 8 * d.col[c].width;
-    int const nbit        = d.col[c].mask != nullptr ? 1 : 0;
+    int const nbit        = d.col[c].mask != nullptr || ((force_null_bit >> c) & 1u) ? 1 : 0;
     plan_field f{};
     f.col        = d.col[c];
     f.invert     = descending ? 1 : 0;
@@ -65,6 +64,8 @@ packed_plan make_plan(table_view const& keys, std::vector<order> const& column_o
   close_word();
   return p;
 }
+
+namespace {
 
 std::unique_ptr<column> order_of(table_view const& keys, std::vector<order> const& column_order,
                                  std::vector<null_order> const& null_precedence, stream_ref stream, rmm::device_async_resource_ref mr)

@@ -1,6 +1,7 @@
 // SPDX-License-Identifier: Apache-2.0
-// The packed radix words of cudf::sorted_order / is_sorted (include/cudf/sorting.hpp): the plan the host makes of a key table
-// (sorting.cpp) and the launchers of the kernels that read it (sorting_kernels.hip).
+// The packed radix words of cudf::sorted_order / is_sorted (include/cudf/sorting.hpp) and of cudf::lower_bound / upper_bound /
+// merge (search.hpp, merge.hpp): the plan the host makes of a key table (sorting.cpp) and the launchers of the kernels that read
+// it (sorting_kernels.hip, search_merge_kernels.hip).
 //
 // Layout. Each key column is a field of vbits + nbit bits: vbits = 1 for BOOL8, otherwise 8 * width; nbit = 1 if the column has
 // nulls, else 0. The columns are walked from the last to the first and each field is placed above the fields already in the
@@ -20,6 +21,8 @@
 #include "../common/device_table.hpp"
 
 #include <hip/hip_runtime.h>
+
+#include <vector>
 
 namespace cudf::detail::sorting {
 
@@ -56,10 +59,43 @@ struct packed_plan {
   }
 };
 
+// Throws unless column_order and null_precedence are empty or have one entry per column of `keys`.
+void check_orders(table_view const& keys, std::vector<order> const& column_order, std::vector<null_order> const& null_precedence);
+// The words of `keys`, least significant first ("Layout"). Bit c of `force_null_bit`: column c gets a null bit even without a mask,
+// so that two tables of one schema get one layout when only one of them has nulls in the column (the side without a mask reads as
+// all valid).
+packed_plan make_plan(table_view const& keys, std::vector<order> const& column_order, std::vector<null_order> const& null_precedence,
+                      uint32_t force_null_bit = 0);
+
 // words[i] = word `w` of row (payload ? payload[i] : i) for i < n; or_and[0] |= word, or_and[1] &= word
 void launch_fill_packed_words(plan_word const& w, uint32_t const* payload, uint64_t* words, uint64_t* or_and, int64_t n, hipStream_t s);
 // *flag (device, zeroed by the caller) becomes non-zero if some row i in [1, n) is lexicographically less than row i - 1; p: the
 // plan in device memory, at least one word
 void launch_is_sorted(packed_plan const* p, int64_t n, uint32_t* flag, hipStream_t s);
+
+// ---- rows of two tables (search_merge_kernels.hip). `plans` is device memory that holds two plans of ONE layout, [0] of the
+// haystack and [1] of the needles (launch_store_plans writes them in stream order); nwords is that layout's word count, at least 1.
+void launch_store_plans(packed_plan const& haystack, packed_plan const& needles, packed_plan* plans, hipStream_t s);
+// out[i] = the number of haystack rows less than (upper: less than or equal to) needle row i, for i < needle_rows
+void launch_bound_search(packed_plan const* plans, int nwords, int64_t haystack_rows, int64_t needle_rows, bool upper, int32_t* out,
+                         hipStream_t s);
+// order[i + bound(i)] = tag | i for every needle row i, with the bound of launch_bound_search; order has haystack_rows +
+// needle_rows entries and every position written is inside it
+void launch_merge_positions(packed_plan const* plans, int nwords, int64_t haystack_rows, int64_t needle_rows, bool upper, uint32_t tag,
+                            uint32_t* order, hipStream_t s);
+
+constexpr uint32_t MERGE_SIDE_B = 0x80000000u;  // an entry of `order`: the side in bit 31, the row of that side's table below
+constexpr int MERGE_COLS        = 4;            // columns per launch of the two-source gather
+struct merge_cols {
+  device_column a[MERGE_COLS];  // column c of side A and of side B: one type; a mask on either, both or neither
+  device_column b[MERGE_COLS];
+  void* out[MERGE_COLS];
+  int32_t ncols;
+};
+// out[c][i] = element (order[i] & ~MERGE_SIDE_B) of a[c] or b[c], by the side bit, for i < n
+void launch_merge_gather(merge_cols const& g, uint32_t const* order, int64_t n, hipStream_t s);
+// out_mask bit i = the validity of that element; *null_count (device, zeroed by the caller) += the nulls
+void launch_merge_mask(device_column const& a, device_column const& b, uint32_t const* order, int64_t n, bitmask_type* out_mask,
+                       int32_t* null_count, hipStream_t s);
 
 }  // namespace cudf::detail::sorting

@@ -246,6 +246,24 @@ cudf_amd_status cudf_amd_is_sorted(const cudf_amd_column_view* input, int32_t nu
                                    int32_t num_order, const int32_t* null_precedence, int32_t num_precedence, void* stream,
                                    int32_t* out);
 
+/* ---- cudf::lower_bound / upper_bound (reference cpp/include/cudf/search.hpp) and cudf::merge (cpp/include/cudf/merge.hpp).
+ * column_order / null_precedence are encoded as for cudf_amd_sorted_order.
+ * cudf_amd_search_bound: upper = 0: lower_bound, 1: upper_bound. out = table of ONE INT32 column of the needles' row count: the
+ * number of haystack rows less than (upper: less than or equal to) each needle row. A length of 0 selects the default order; any
+ * other length that differs from num_columns returns CUDF_AMD_LOGIC_ERROR, and haystack and needles of different column counts or
+ * types return CUDF_AMD_INVALID_ARGUMENT.
+ * cudf_amd_merge: `tables` points to num_tables arrays of num_columns column views each, every table sorted on its columns
+ * key_cols under the orders (num_order must equal num_keys: an empty column_order is an error here; num_precedence 0 means BEFORE).
+ * out = every row of every table, sorted on the key columns. Every rejected input of include/cudf/merge.hpp returns
+ * CUDF_AMD_LOGIC_ERROR. num_tables == 0 gives a table of zero columns. */
+cudf_amd_status cudf_amd_search_bound(const cudf_amd_column_view* haystack, int32_t num_columns, const cudf_amd_column_view* needles,
+                                      int32_t num_needle_columns, const int32_t* column_order, int32_t num_order,
+                                      const int32_t* null_precedence, int32_t num_precedence, int32_t upper, void* stream,
+                                      cudf_amd_table_t* out);
+cudf_amd_status cudf_amd_merge(const cudf_amd_column_view* const* tables, int32_t num_tables, int32_t num_columns,
+                               const int32_t* key_cols, int32_t num_keys, const int32_t* column_order, int32_t num_order,
+                               const int32_t* null_precedence, int32_t num_precedence, void* stream, cudf_amd_table_t* out);
+
 /* ---- Arrow C Data Interface (reference cpp/include/cudf/interop.hpp: from_arrow :685-689, to_arrow_host :618-621,
  * to_arrow_schema :473-475). The structs are the ones the Arrow specification publishes.
  * cudf_amd_from_arrow: host Arrow struct array (one child per column) -> owning device table; the input is not
