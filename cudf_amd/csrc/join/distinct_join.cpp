@@ -4,13 +4,10 @@
 // Build forms and kernels: distinct_join_impl.hpp, distinct_join_kernels.hip; the model: DESIGN.md section 4, "Joins on a
 // unique-key build table".
 #include "distinct_join_impl.hpp"
-#include "filtered_join_impl.hpp"
-#include "hash_join_impl.hpp"
 #include "../common/profiler.hpp"
+#include "../common/row_set_host.hpp"
 
 #include <algorithm>
-#include <cmath>
-#include <stdexcept>
 
 namespace cudf {
 namespace detail {
@@ -36,29 +33,24 @@ void distinct_join_impl::alloc_side(hipStream_t s)
   _table.side = static_cast<size_type*>(_side.data());
 }
 
-// One integer key column (1, 2, 4 or 8 bytes; timestamps, durations, decimals and bool included) whose valid build keys span a
-// small range takes the direct table. 1- and 2-byte keys take it over their whole type range (at most 2^16 entries). 4- and 8-byte
-// keys take it when the range [min, max] of their valid build keys is at most CUDF_AMD_DJOIN_DENSE_RATIO (8) entries per build row
-// and the table at most CUDF_AMD_DJOIN_DENSE_MAX_BYTES (2^31) bytes. CUDF_AMD_DJOIN_DENSE=0 sends every key to the map.
+// One integer or bool key column whose valid build keys span a small range takes the direct table (rowset::small_key_range): at
+// most CUDF_AMD_DJOIN_DENSE_RATIO (8) entries per build row and the table at most CUDF_AMD_DJOIN_DENSE_MAX_BYTES (2^31) bytes.
+// CUDF_AMD_DJOIN_DENSE=0 sends every key to the map.
 bool distinct_join_impl::try_direct_build(stream_ref stream)
 {
   if (_right.num_columns() != 1 || env_i64("CUDF_AMD_DJOIN_DENSE", 1) == 0) return false;
   device_column const& c = _table.build.col[0];
-  if (c.cls != CLS_SINT && c.cls != CLS_UINT && c.cls != CLS_BOOL) return false;
-  hipStream_t const s = stream.value();
-  auto const rows     = static_cast<uint64_t>(_right.num_rows());
-  uint64_t lo = 0, range = 0;
-  if (c.width <= 2) {
-    range = uint64_t{1} << (8 * c.width);  // entry = the key's raw bits
-  } else {
-    if (!fjoin::valid_key_range(c, _right.num_rows(), lo, range, s)) return false;
-    auto const ratio     = static_cast<uint64_t>(std::clamp<int64_t>(env_i64("CUDF_AMD_DJOIN_DENSE_RATIO", 8), 0, int64_t{1} << 32));
-    auto const max_bytes = static_cast<uint64_t>(std::max<int64_t>(env_i64("CUDF_AMD_DJOIN_DENSE_MAX_BYTES", int64_t{1} << 31), 0));
-    if (range > max_bytes / sizeof(size_type) || range > ratio * rows) return false;
-    if (range == 0 && !_table.nulls_equal) return true;  // no valid build key and a NULL matches nothing: the empty form
-    if (c.width == 4) lo &= 0xffffffffu;  // (valid_key_range widens to 64 bits; the table counts within the key's width)
-  }
-  auto const entries = static_cast<std::size_t>(std::max<uint64_t>(range, 1));
+  hipStream_t const s    = stream.value();
+  auto const ratio       = static_cast<uint64_t>(std::clamp<int64_t>(env_i64("CUDF_AMD_DJOIN_DENSE_RATIO", 8), 0, int64_t{1} << 32));
+  auto const max_bytes   = static_cast<uint64_t>(std::max<int64_t>(env_i64("CUDF_AMD_DJOIN_DENSE_MAX_BYTES", int64_t{1} << 31), 0));
+  auto const r = rowset::small_key_range(c, _right.num_rows(), _right.num_rows(), ratio, max_bytes / sizeof(size_type), s, true);
+  if (!r) return false;
+  if (r->range == 0 && !_table.nulls_equal) return true;  // no valid build key and a NULL matches nothing: the empty form
+  // the table counts within the key's width: 1- and 2-byte keys index it by their raw bits, and of the first key of a 4-byte
+  // column (which small_key_range widens to 64 bits) it keeps the raw bits
+  uint64_t const range = r->range;
+  uint64_t const lo    = c.width <= 2 ? 0 : c.width == 4 ? r->lo & 0xffffffffu : r->lo;
+  auto const entries   = static_cast<std::size_t>(std::max<uint64_t>(range, 1));
   _entries           = rmm::device_buffer{entries * sizeof(size_type), s, _mr};
   CUDF_HIP_TRY(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(_entries.data()), JoinNoMatch, entries, s));
   alloc_side(s);
@@ -70,19 +62,15 @@ bool distinct_join_impl::try_direct_build(stream_ref stream)
   return true;
 }
 
-// The open-addressing map of the build rows: ceil(rows / load_factor) slots, at least rows + 1 (so that at load factor 1 a key that
-// is absent still reaches an empty slot and the probe loop ends), counted in 64 bits.
+// The open-addressing map of the build rows (rowset::set_capacity slots).
 void distinct_join_impl::map_build(double load_factor, stream_ref stream)
 {
-  hipStream_t const s    = stream.value();
-  auto const rows        = static_cast<double>(_right.num_rows());
-  device_column const& c = _table.build.col[0];
-  double const slots     = std::max(std::ceil(rows / load_factor), rows + 1);
-  CUDF_EXPECTS(slots < 0x1p58, "distinct_hash_join: the hash map of this load factor exceeds the addressable memory", std::overflow_error);
-  bool const one_key = _right.num_columns() == 1 && (c.cls == CLS_SINT || c.cls == CLS_UINT || c.cls == CLS_F32 || c.cls == CLS_F64);
-  auto const kind    = one_key && c.width == 4 ? djoin::map_kind::key4 : one_key && c.width == 8 ? djoin::map_kind::key8 : djoin::map_kind::rows;
-  _table.capacity    = static_cast<uint64_t>(slots);
-  _table.kind        = static_cast<int32_t>(kind);
+  hipStream_t const s = stream.value();
+  auto const kind     = !rowset::inline_key_column(_table.build) ? djoin::map_kind::rows
+                        : _table.build.col[0].width == 4         ? djoin::map_kind::key4
+                                                                 : djoin::map_kind::key8;
+  _table.capacity     = rowset::set_capacity(_right.num_rows(), load_factor, "distinct_hash_join: the hash map");
+  _table.kind         = static_cast<int32_t>(kind);
   _entries = rmm::device_buffer{static_cast<std::size_t>(_table.capacity) * (kind == djoin::map_kind::key8 ? 16 : 8), s, _mr};
   CUDF_HIP_TRY(hipMemsetAsync(_entries.data(), 0xff, _entries.size(), s));
   alloc_side(s);
@@ -91,17 +79,10 @@ void distinct_join_impl::map_build(double load_factor, stream_ref stream)
   djoin::launch_build(_table, s);
 }
 
-void distinct_join_impl::validate_probe(table_view const& left) const
-{
-  // as filtered_join and hash_join (join.cpp validate_probe); the reference checks nothing here
-  CUDF_EXPECTS(0 != left.num_columns(), "Distinct hash join left table is empty", std::invalid_argument);
-  CUDF_EXPECTS(_right.num_columns() == left.num_columns(), "Mismatch in number of columns to be joined on", std::invalid_argument);
-  CUDF_EXPECTS(same_types(_right, left), "Mismatch in joining column data types", cudf::data_type_error);
-}
-
 djoin::probe_args distinct_join_impl::probe_args_of(table_view const& left) const
 {
-  fjoin::geometry const g = fjoin::geometry_of(left.num_rows());
+  rowset::validate_probe(_right, left, "Distinct hash join");  // (the reference checks nothing here)
+  rowset::geometry const g = rowset::geometry_of(left.num_rows());
   djoin::probe_args a{};
   a.probe  = make_device_table(left);
   a.t      = _table;
@@ -117,17 +98,14 @@ join_index_pair distinct_join_impl::inner_join(table_view const& left, stream_re
   int64_t const n     = left.num_rows();
   // trivial cases first, as the reference (distinct_hash_join.cu inner_join): no left rows, or no right rows
   if (n == 0 || _table.table_form == static_cast<int32_t>(djoin::form::empty)) return alloc_pairs(0, s, mr);
-  validate_probe(left);
-  auto tmp            = cudf::get_current_device_resource_ref();
   djoin::probe_args a = probe_args_of(left);
-  rmm::device_buffer found{static_cast<std::size_t>(n) * sizeof(size_type), s, tmp};
-  rmm::device_buffer mask{static_cast<std::size_t>((n + 63) / 64) * sizeof(uint64_t), s, tmp};
-  rmm::device_buffer counts{static_cast<std::size_t>(a.nwaves + 1) * sizeof(unsigned long long), s, tmp};
+  rmm::device_buffer found{static_cast<std::size_t>(n) * sizeof(size_type), s, cudf::get_current_device_resource_ref()};
+  rowset::compaction c{n, s};
   a.found  = static_cast<size_type*>(found.data());
-  a.mask   = static_cast<uint64_t*>(mask.data());
-  a.counts = static_cast<unsigned long long*>(counts.data());
+  a.mask   = c.mask();
+  a.counts = c.counts();
   djoin::launch_probe(a, s);
-  auto const total = scan_total(a.counts, a.nwaves, s);  // (the one read-back: sizes the output exactly)
+  auto const total = c.total(s);
   auto out         = alloc_pairs(static_cast<std::size_t>(total), s, mr);
   a.out_left       = out.first->data();
   a.out_right      = out.second->data();
@@ -149,7 +127,6 @@ std::unique_ptr<rmm::device_uvector<size_type>> distinct_join_impl::left_join(ta
     CUDF_HIP_TRY(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(out->data()), JoinNoMatch, static_cast<std::size_t>(n), s));
     return out;
   }
-  validate_probe(left);
   djoin::probe_args a = probe_args_of(left);
   a.found             = out->data();
   djoin::launch_probe(a, s);

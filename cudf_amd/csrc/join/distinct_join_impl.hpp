@@ -6,7 +6,7 @@
 //  - direct: one integer (or bool) key column whose valid build keys span a small range [lo, lo + range): a size_type array over
 //    the range, preset to JoinNoMatch, build row r stored at key - lo with a plain store. A probe is a range test and one 4-byte
 //    load; a key outside the range touches no memory.
-//  - map: an open-addressing table in HBM, linear probing (set_device.hpp), one of three slot layouts (map_kind).
+//  - map: the open-addressing table of common/row_set.hpp in HBM, one of three slot layouts (map_kind).
 // In the single-column layouts a NULL key is never inserted: the build keeps the row of a NULL build key in a side word (nulls
 // EQUAL only), and a NULL probe key answers that word. Both side words live in device memory, so that neither the constructor nor
 // a probe reads them back.
@@ -21,8 +21,6 @@
 namespace cudf::detail {
 namespace djoin {
 
-constexpr uint64_t MAP_EMPTY = ~uint64_t{0};  // an unused slot (no entry has this value, see map_kind)
-
 enum class form : int32_t {
   empty,   // no build rows, or none that can match
   direct,  // one integer key column over a small range
@@ -32,7 +30,7 @@ enum class form : int32_t {
 enum class map_kind : int32_t {
   key4,  // one 4-byte key column: an 8-byte slot {normalised key bits << 32 | build row}, claimed with one CAS
   key8,  // one 8-byte key column: a 16-byte slot {normalised key bits, build row}; the key is claimed with a 64-bit CAS, the row
-         // stored after it (probes run after the build kernel has ended). The key MAP_EMPTY goes to side[1] instead.
+         // stored after it (probes run after the build kernel has ended). The key rowset::EMPTY goes to side[1] instead.
   rows,  // any other key: an 8-byte slot {32-bit row hash << 32 | build row}, rows compared with rows_equal
 };
 
@@ -48,15 +46,14 @@ struct table_args {
   // map
   uint64_t* slots;      // capacity slots of 8 bytes (key4, rows) or 16 bytes (key8)
   uint64_t capacity;    // > the build rows: every probe sequence ends at an empty slot
-  // single-column layouts: side[0] = the row of a NULL build key (nulls EQUAL), side[1] = the row of the 8-byte key MAP_EMPTY;
+  // single-column layouts: side[0] = the row of a NULL build key (nulls EQUAL), side[1] = the row of the 8-byte key rowset::EMPTY;
   // JoinNoMatch when there is none
   size_type* side;
 };
 
-// The probe. Left rows are cut into `nwaves` contiguous chunks of `chunk` rows (fjoin::geometry_of), one per wave. The pass writes
-// found[i] = the build row of left row i or JoinNoMatch. For left_join that is the result. For inner_join (mask != nullptr) it
-// also writes one ballot word per 64 rows and the number of matches per chunk; after scan_total the compaction writes
-// {i, found[i]} of the set bits at chunk offset + word prefix + mbcnt, ascending.
+// The probe (rowset::probe_chunk over rowset::geometry_of's chunks). The pass writes found[i] = the build row of left row i or
+// JoinNoMatch. For left_join that is the result. For inner_join (mask != nullptr) it also fills the scratch of a rowset::compaction,
+// and after its scan the compaction writes {i, found[i]} of the set bits, ascending.
 struct probe_args {
   device_table probe;
   table_args t;
@@ -86,7 +83,6 @@ class distinct_join_impl {
                                                                           rmm::device_async_resource_ref mr) const;
 
  private:
-  void validate_probe(table_view const& left) const;
   bool try_direct_build(stream_ref stream);
   void map_build(double load_factor, stream_ref stream);
   void alloc_side(hipStream_t s);

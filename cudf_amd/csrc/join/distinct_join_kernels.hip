@@ -3,30 +3,17 @@
 // one build row per left row, and the ordered compaction of the matches into {left, right} index pairs. Replaces the reference's
 // cuco::static_set insert / find and thrust copy_if (cpp/src/join/distinct_hash_join.cu).
 #include "distinct_join_impl.hpp"
-#include "set_device.hpp"
 #include "../common/profiler.hpp"
-
-#include <cudf/utilities/error.hpp>
-
-#include <algorithm>
+#include "../common/row_set.hpp"
 
 namespace cudf::detail::djoin {
 namespace {
 
-using fjoin::compact_chunk;
-using fjoin::home_slot;
-using fjoin::load_bits;
-using fjoin::load_int;
-using fjoin::next_slot;
+using namespace rowset;
 
 constexpr int THREADS = 256;  // 4 waves per workgroup
 
 // ------------------------------------------------------------------ keys
-struct col_key {
-  uint64_t v;
-  bool valid;
-};
-
 // The entry of the direct table that the raw bits of a W-byte key select: key - lo, wrapping within W bytes. The wrap makes the
 // subtraction right for signed and unsigned columns alike (lo holds the raw bits of the smallest key of the column's own order).
 template <int W>
@@ -78,28 +65,17 @@ __global__ void __launch_bounds__(THREADS) k_build_key(table_args a)
       continue;
     }
     uint64_t const key = normalize_key_bits(load_bits<W>(c, i), c.cls);
-    if (W == 8 && key == MAP_EMPTY) {  // the one value a slot's key word cannot hold
+    if (W == 8 && key == EMPTY) {  // the one value a slot's key word cannot hold
       sentinel_row = static_cast<size_type>(i);
       continue;
     }
     // the word that claims the slot: the key itself (8 bytes), or the key above the row (4 bytes; a row is < 2^31, so no entry
-    // equals MAP_EMPTY)
+    // equals EMPTY). A duplicate key: the row that claimed the slot stays.
     uint64_t const entry = W == 8 ? key : (key << 32) | static_cast<uint32_t>(i);
-    uint64_t s           = home_slot(murmur3_32_bits(key, W, 0), a.capacity);
-    while (true) {
-      uint64_t* const word = a.slots + (W == 8 ? 2 * s : s);
-      uint64_t cur         = gload(word);
-      if (cur == MAP_EMPTY) {
-        cur = atomicCAS(reinterpret_cast<unsigned long long*>(word), static_cast<unsigned long long>(MAP_EMPTY),
-                        static_cast<unsigned long long>(entry));
-        if (cur == MAP_EMPTY) {  // claimed; the 16-byte slot takes its row next to the key
-          if constexpr (W == 8) gstore(reinterpret_cast<uint32_t*>(word + 1), static_cast<uint32_t>(i));
-          break;
-        }
-      }
-      if ((W == 8 ? cur : cur >> 32) == key) break;  // a duplicate key: the row that claimed the slot stays
-      s = next_slot(s, a.capacity);
-    }
+    auto const got       = claim(a.slots, W == 8 ? 2 : 1, a.capacity, home_slot(murmur3_32_bits(key, W, 0), a.capacity), entry,
+                                 [&](uint64_t cur) { return (W == 8 ? cur : cur >> 32) == key; });
+    // the 16-byte slot takes its row next to the key
+    if (W == 8 && got.inserted) gstore(reinterpret_cast<uint32_t*>(a.slots + 2 * got.slot + 1), static_cast<uint32_t>(i));
   }
   if (a.nulls_equal) store_side(a.side, null_row);
   if constexpr (W == 8) store_side(a.side + 1, sentinel_row);
@@ -112,31 +88,27 @@ __global__ void __launch_bounds__(THREADS) k_build_rows(table_args a)
   bool const eq        = a.nulls_equal != 0;
   for (int64_t i = blockIdx.x * static_cast<int64_t>(blockDim.x) + threadIdx.x; i < n; i += stride) {
     if (!eq && row_has_null(a.build, i)) continue;  // null_equality::UNEQUAL: such a row equals no row
-    uint32_t const h     = row_hash(a.build, i, 0);
-    uint64_t const entry = (static_cast<uint64_t>(h) << 32) | static_cast<uint32_t>(i);
-    uint64_t s           = home_slot(h, a.capacity);
-    while (true) {
-      uint64_t cur = gload(a.slots + s);
-      if (cur == MAP_EMPTY) {
-        cur = atomicCAS(reinterpret_cast<unsigned long long*>(a.slots + s), static_cast<unsigned long long>(MAP_EMPTY),
-                        static_cast<unsigned long long>(entry));
-        if (cur == MAP_EMPTY) break;
-      }
-      if ((cur >> 32) == h && rows_equal(a.build, static_cast<uint32_t>(cur), a.build, i, eq)) break;  // a duplicate row
-      s = next_slot(s, a.capacity);
-    }
+    uint32_t const h = row_hash(a.build, i, 0);
+    claim(a.slots, 1, a.capacity, home_slot(h, a.capacity), (static_cast<uint64_t>(h) << 32) | static_cast<uint32_t>(i), [&](uint64_t cur) {
+      return (cur >> 32) == h && rows_equal(a.build, static_cast<uint32_t>(cur), a.build, i, eq);  // a duplicate row
+    });
   }
 }
 
 // ------------------------------------------------------------------ the probe: one build row per left row
-// load(r): what the lookup needs of left row r, fetched ahead; find(key, r): the equal build row or JoinNoMatch.
+// The build row of a {key or hash | row} word that rowset::find returned; EMPTY: the key is absent.
+__device__ __forceinline__ size_type row_of(uint64_t word)
+{
+  return word == EMPTY ? JoinNoMatch : static_cast<size_type>(static_cast<uint32_t>(word));
+}
+
+// load(r): what the lookup needs of left row r, fetched ahead; lookup(key, r): the equal build row or JoinNoMatch.
 template <int W>
 struct direct_lookup {
   static constexpr int UNROLL = 8;
-  using key_t                 = col_key;
   probe_args const& a;
-  __device__ col_key load(int64_t r) const { return {load_int<W, false>(a.probe.col[0], r), col_is_valid(a.probe.col[0], r)}; }
-  __device__ size_type find(col_key k, int64_t) const
+  __device__ key load(int64_t r) const { return {load_int<W, false>(a.probe.col[0], r), col_is_valid(a.probe.col[0], r)}; }
+  __device__ size_type lookup(key k, int64_t) const
   {
     if (!k.valid) return gload(a.t.side);
     uint64_t const off = direct_entry<W>(a.t, a.probe.col[0], k.v);
@@ -148,94 +120,60 @@ struct direct_lookup {
 template <int W>
 struct key_lookup {
   static constexpr int UNROLL = 4;
-  using key_t                 = col_key;
   probe_args const& a;
-  __device__ col_key load(int64_t r) const
+  __device__ key load(int64_t r) const
   {
     device_column const& c = a.probe.col[0];
     return {normalize_key_bits(load_bits<W>(c, r), c.cls), col_is_valid(c, r)};
   }
-  __device__ size_type find(col_key k, int64_t) const
+  __device__ size_type lookup(key k, int64_t) const
   {
     if (!k.valid) return gload(a.t.side);
-    if (W == 8 && k.v == MAP_EMPTY) return gload(a.t.side + 1);
+    if (W == 8 && k.v == EMPTY) return gload(a.t.side + 1);
     uint64_t s = home_slot(murmur3_32_bits(k.v, W, 0), a.t.capacity);
-    while (true) {
-      if constexpr (W == 8) {
-        u64x2 const cur = gload(reinterpret_cast<u64x2 const*>(a.t.slots) + s);  // key and row in one 16-byte load
+    if constexpr (W == 8) {
+      // rowset::find's walk, written out: it loads one word per slot, and this slot's key and row come in one 16-byte load
+      while (true) {
+        u64x2 const cur = gload(reinterpret_cast<u64x2 const*>(a.t.slots) + s);
         if (cur.x == k.v) return static_cast<size_type>(static_cast<uint32_t>(cur.y));
-        if (cur.x == MAP_EMPTY) return JoinNoMatch;
-      } else {
-        uint64_t const cur = gload(a.t.slots + s);
-        if (cur == MAP_EMPTY) return JoinNoMatch;
-        if ((cur >> 32) == k.v) return static_cast<size_type>(static_cast<uint32_t>(cur));
+        if (cur.x == EMPTY) return JoinNoMatch;
+        s = next_slot(s, a.t.capacity);
       }
-      s = next_slot(s, a.t.capacity);
+    } else {
+      return row_of(find(a.t.slots, 1, a.t.capacity, s, [&](uint64_t cur) { return (cur >> 32) == k.v; }));
     }
   }
 };
 
 struct rows_lookup {
   static constexpr int UNROLL = 1;
-  struct key_t {};
   probe_args const& a;
-  __device__ key_t load(int64_t) const { return {}; }
-  __device__ size_type find(key_t, int64_t r) const
+  __device__ no_key load(int64_t) const { return {}; }
+  __device__ size_type lookup(no_key, int64_t r) const
   {
     bool const eq = a.t.nulls_equal != 0;
     if (!eq && row_has_null(a.probe, r)) return JoinNoMatch;
     uint32_t const h = row_hash(a.probe, r, 0);
-    uint64_t s       = home_slot(h, a.t.capacity);
-    while (true) {
-      uint64_t const cur = gload(a.t.slots + s);
-      if (cur == MAP_EMPTY) return JoinNoMatch;
-      if ((cur >> 32) == h && rows_equal(a.probe, r, a.t.build, static_cast<uint32_t>(cur), eq))
-        return static_cast<size_type>(static_cast<uint32_t>(cur));
-      s = next_slot(s, a.t.capacity);
-    }
+    return row_of(find(a.t.slots, 1, a.t.capacity, home_slot(h, a.t.capacity), [&](uint64_t cur) {
+      return (cur >> 32) == h && rows_equal(a.probe, r, a.t.build, static_cast<uint32_t>(cur), eq);
+    }));
   }
 };
 
-// Wave `wave` answers rows [wave * chunk, + chunk) of the left table, UNROLL x 64 rows at a time: every lane first loads its rows'
-// keys (clamped to the chunk, so that the loads need no branch and stay in flight together), then looks them up and writes the
-// rows found, coalesced. COMPACT (inner_join): the ballot of a 64-row group is its mask word, their sum the chunk's count.
+// rowset::probe_chunk over the left table: each row is looked up and the row found written, coalesced. COMPACT (inner_join): with
+// the mask words and the chunk counts of the rows that found one.
 template <bool COMPACT, typename Lookup>
 __global__ void __launch_bounds__(THREADS) k_probe(probe_args a)
 {
-  constexpr int UNROLL = Lookup::UNROLL;
   Lookup const p{a};
-  int const lane       = threadIdx.x & 63;
-  int64_t const wave   = static_cast<int64_t>(blockIdx.x) * (THREADS / 64) + (threadIdx.x >> 6);
-  int64_t const begin  = wave * a.chunk;
-  int64_t const end    = a.nrows < begin + a.chunk ? a.nrows : begin + a.chunk;
-  unsigned long long n = 0;
-  for (int64_t r0 = begin; r0 < end; r0 += UNROLL * 64) {
-    typename Lookup::key_t k[UNROLL];
-#pragma unroll
-    for (int j = 0; j < UNROLL; ++j) {
-      int64_t const r = r0 + j * 64 + lane;
-      k[j]            = p.load(r < end ? r : end - 1);
-    }
-#pragma unroll
-    for (int j = 0; j < UNROLL; ++j) {
-      int64_t const r = r0 + j * 64 + lane;
-      size_type f     = JoinNoMatch;
-      if (r < end) {
-        f = p.find(k[j], r);
-        gstore(a.found + r, f);
-      }
-      if constexpr (COMPACT) {
-        uint64_t const m = __ballot(f != JoinNoMatch);
-        if (r0 + j * 64 < end) {
-          if (lane == 0) gstore(a.mask + ((r0 + j * 64) >> 6), m);
-          n += __popcll(m);
-        }
-      }
-    }
-  }
-  if constexpr (COMPACT) {
-    if (lane == 0 && wave < a.nwaves) gstore(a.counts + wave, n);
-  }
+  int64_t const wave = static_cast<int64_t>(blockIdx.x) * (THREADS / 64) + (threadIdx.x >> 6);
+  probe_chunk<Lookup::UNROLL, COMPACT>(
+    a, wave, [&](int64_t r) { return p.load(r); },
+    [&](auto const& k, int64_t r) {
+      size_type const f = p.lookup(k, r);
+      gstore(a.found + r, f);
+      return f != JoinNoMatch;
+    });
 }
 
 // ------------------------------------------------------------------ inner_join, pass 2: ordered compaction of the pairs
@@ -247,23 +185,6 @@ __global__ void __launch_bounds__(THREADS) k_compact_pairs(probe_args a)
     gstore(a.out_left + o, static_cast<size_type>(row));
     gstore(a.out_right + o, gload(a.found + row));
   });
-}
-
-unsigned blocks_for(int64_t n)
-{
-  return static_cast<unsigned>(std::clamp<int64_t>((n + THREADS - 1) / THREADS, 1, 256 * 16));
-}
-
-template <typename F>
-void dispatch_width(int width, F&& f)
-{
-  switch (width) {
-    case 1: return f.template operator()<1>();
-    case 2: return f.template operator()<2>();
-    case 4: return f.template operator()<4>();
-    case 8: return f.template operator()<8>();
-    default: CUDF_FAIL("distinct_hash_join: the direct table takes 1-, 2-, 4- or 8-byte keys");
-  }
 }
 
 template <bool COMPACT>
@@ -286,7 +207,7 @@ void launch_build(table_args const& a, hipStream_t stream)
 {
   bool const direct = a.table_form == static_cast<int32_t>(form::direct);
   cudf::detail::prof::scope prof_{direct ? "djoin_build_direct" : "djoin_build_map", stream};
-  dim3 const grid(blocks_for(a.build.nrows)), block(THREADS);
+  dim3 const grid(grid_for(a.build.nrows, THREADS)), block(THREADS);
   if (direct) {
     dispatch_width(a.build.col[0].width, [&]<int W>() { hipLaunchKernelGGL((k_build_direct<W>), grid, block, 0, stream, a); });
   } else if (a.kind == static_cast<int32_t>(map_kind::key4)) {

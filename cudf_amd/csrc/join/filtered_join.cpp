@@ -3,12 +3,10 @@
 // the two probes. Reference counterpart: cpp/src/join/filtered_join/filtered_join.cu (constructor, semi_anti_join, semi_join,
 // anti_join). Build forms and kernels: filtered_join_impl.hpp, filtered_join_kernels.hip; the model: DESIGN.md section 4, "Semi and anti joins".
 #include "filtered_join_impl.hpp"
-#include "hash_join_impl.hpp"
 #include "../common/profiler.hpp"
+#include "../common/row_set_host.hpp"
 
 #include <algorithm>
-#include <cmath>
-#include <stdexcept>
 
 namespace cudf {
 namespace detail {
@@ -19,32 +17,6 @@ std::unique_ptr<rmm::device_uvector<size_type>> no_rows(stream_ref stream, rmm::
   return std::make_unique<rmm::device_uvector<size_type>>(0, stream.value(), mr);
 }
 }  // namespace
-
-namespace fjoin {
-bool valid_key_range(device_column const& c, int64_t rows, uint64_t& lo, uint64_t& range, hipStream_t s)
-{
-  bool const is_signed = c.cls == CLS_SINT;
-  auto tmp             = cudf::get_current_device_resource_ref();
-  join::join_args a{};
-  a.build.ncols  = 1;
-  a.build.nrows  = static_cast<int32_t>(rows);
-  a.build.col[0] = c;
-  a.check_nulls  = 1;
-  rmm::device_buffer mm{2 * sizeof(uint64_t), s, tmp}, d_args{sizeof(join::join_args), s, tmp};
-  join::launch_key_minmax(a, static_cast<join::join_args*>(d_args.data()), is_signed ? 1 : 0, static_cast<uint64_t*>(mm.data()), s);
-  uint64_t h[2] = {0, 0};
-  CUDF_HIP_TRY(hipMemcpyAsync(h, mm.data(), sizeof(h), hipMemcpyDeviceToHost, s));
-  CUDF_HIP_TRY(hipStreamSynchronize(s));
-  bool const any_valid = is_signed ? static_cast<int64_t>(h[0]) <= static_cast<int64_t>(h[1]) : h[0] <= h[1];
-  lo = range = 0;
-  if (!any_valid) return true;  // (no valid key: an empty range)
-  uint64_t const width = h[1] - h[0];  // exact in two's complement for either ordering
-  if (width == ~uint64_t{0}) return false;
-  lo    = h[0];
-  range = width + 1;
-  return true;
-}
-}  // namespace fjoin
 
 filtered_join_impl::filtered_join_impl(table_view const& right, null_equality compare_nulls, double load_factor, stream_ref stream,
                                        rmm::device_async_resource_ref mr)
@@ -57,31 +29,21 @@ filtered_join_impl::filtered_join_impl(table_view const& right, null_equality co
   set_build(load_factor, stream);
 }
 
-// One integer key column (1, 2, 4 or 8 bytes; timestamps, durations and decimals included) whose valid build keys span a small range
-// takes the bitmap. 1- and 2-byte keys take it over their whole type range (at most 2^16 bits). 4- and 8-byte keys take it when the
-// range [min, max] of their valid build keys is at most CUDF_AMD_FJOIN_DENSE_RATIO (32) bits per build row and at most
-// CUDF_AMD_FJOIN_DENSE_MAX_BITS (2^31: 256 MiB, the Infinity Cache) bits. CUDF_AMD_FJOIN_DENSE=0 sends every key to the hash set.
+// One integer key column whose valid build keys span a small range takes the bitmap (rowset::small_key_range): at most
+// CUDF_AMD_FJOIN_DENSE_RATIO (32) bits per build row and at most CUDF_AMD_FJOIN_DENSE_MAX_BITS (2^31: 256 MiB, the Infinity Cache)
+// bits. CUDF_AMD_FJOIN_DENSE=0 sends every key to the hash set.
 bool filtered_join_impl::try_bitmap_build(stream_ref stream)
 {
   if (_right.num_columns() != 1 || env_i64("CUDF_AMD_FJOIN_DENSE", 1) == 0) return false;
   device_column const& c = _build_dev.col[0];
-  if (c.cls != CLS_SINT && c.cls != CLS_UINT) return false;
-  hipStream_t const s   = stream.value();
-  auto const rows       = static_cast<uint64_t>(_right.num_rows());
-  bool const is_signed  = c.cls == CLS_SINT;
-  uint64_t lo = 0, range = 0;
-  if (c.width <= 2) {
-    range = uint64_t{1} << (8 * c.width);
-    lo    = is_signed ? static_cast<uint64_t>(-static_cast<int64_t>(range / 2)) : 0;
-  } else {
-    if (!fjoin::valid_key_range(c, _right.num_rows(), lo, range, s)) return false;
-    auto const ratio    = static_cast<uint64_t>(std::clamp<int64_t>(env_i64("CUDF_AMD_FJOIN_DENSE_RATIO", 32), 0, int64_t{1} << 32));
-    auto const max_bits = static_cast<uint64_t>(std::max<int64_t>(env_i64("CUDF_AMD_FJOIN_DENSE_MAX_BITS", int64_t{1} << 31), 0));
-    if (range > max_bits || range > ratio * rows) return false;
-  }
-  _lo    = lo;
-  _range = range;
-  _bits  = rmm::device_buffer{std::max<std::size_t>(1, static_cast<std::size_t>((range + 127) >> 7)) * 16, s, _mr};
+  hipStream_t const s    = stream.value();
+  auto const ratio       = static_cast<uint64_t>(std::clamp<int64_t>(env_i64("CUDF_AMD_FJOIN_DENSE_RATIO", 32), 0, int64_t{1} << 32));
+  auto const max_bits    = static_cast<uint64_t>(std::max<int64_t>(env_i64("CUDF_AMD_FJOIN_DENSE_MAX_BITS", int64_t{1} << 31), 0));
+  auto const r           = rowset::small_key_range(c, _right.num_rows(), _right.num_rows(), ratio, max_bits, s);
+  if (!r) return false;
+  _lo    = r->lo;
+  _range = r->range;
+  _bits  = rmm::device_buffer{std::max<std::size_t>(1, static_cast<std::size_t>((_range + 127) >> 7)) * 16, s, _mr};
   CUDF_HIP_TRY(hipMemsetAsync(_bits.data(), 0, _bits.size(), s));
   dev_scalar<int32_t> seen_null{0, s};
   fjoin::bitmap_args b{};
@@ -97,21 +59,15 @@ bool filtered_join_impl::try_bitmap_build(stream_ref stream)
   return true;
 }
 
-// The open-addressing set of the distinct build rows: ceil(rows / load_factor) slots (at least rows + 1, so that every probe
-// sequence ends at an empty slot), counted in 64 bits.
+// The open-addressing set of the distinct build rows (rowset::set_capacity slots).
 void filtered_join_impl::set_build(double load_factor, stream_ref stream)
 {
-  hipStream_t const s   = stream.value();
-  auto const rows       = static_cast<double>(_right.num_rows());
-  device_column const& c = _build_dev.col[0];
-  double const slots    = std::max(std::ceil(rows / load_factor), rows + 1);
-  CUDF_EXPECTS(slots < 0x1p58, "filtered_join: the hash set of this load factor exceeds the addressable memory", std::overflow_error);
-  _capacity   = static_cast<uint64_t>(slots);
-  _inline_key = _right.num_columns() == 1 && (c.width == 4 || c.width == 8) &&
-                (c.cls == CLS_SINT || c.cls == CLS_UINT || c.cls == CLS_F32 || c.cls == CLS_F64);
+  hipStream_t const s = stream.value();
+  _capacity           = rowset::set_capacity(_right.num_rows(), load_factor, "filtered_join: the hash set");
+  _inline_key         = rowset::inline_key_column(_build_dev);
   _slots = rmm::device_buffer{static_cast<std::size_t>(_capacity) * sizeof(uint64_t), s, _mr};
   CUDF_HIP_TRY(hipMemsetAsync(_slots.data(), 0xff, _slots.size(), s));
-  dev_scalar<uint64_t> seen{0, s};  // {NULL key, SET_EMPTY key}
+  dev_scalar<uint64_t> seen{0, s};  // {NULL key, rowset::EMPTY key}
   fjoin::set_args a{};
   a.build         = _build_dev;
   a.slots         = static_cast<uint64_t*>(_slots.data());
@@ -127,14 +83,6 @@ void filtered_join_impl::set_build(double load_factor, stream_ref stream)
   _form                = fjoin::form::set;
 }
 
-void filtered_join_impl::validate_probe(table_view const& left) const
-{
-  // as hash_join (join.cpp validate_probe; reference hash_join.cu:47-59)
-  CUDF_EXPECTS(0 != left.num_columns(), "Filtered join left table is empty", std::invalid_argument);
-  CUDF_EXPECTS(_right.num_columns() == left.num_columns(), "Mismatch in number of columns to be joined on", std::invalid_argument);
-  CUDF_EXPECTS(same_types(_right, left), "Mismatch in joining column data types", cudf::data_type_error);
-}
-
 std::unique_ptr<rmm::device_uvector<size_type>> filtered_join_impl::probe(table_view const& left, bool anti, stream_ref stream,
                                                                           rmm::device_async_resource_ref mr) const
 {
@@ -148,21 +96,18 @@ std::unique_ptr<rmm::device_uvector<size_type>> filtered_join_impl::probe(table_
     fjoin::launch_fjoin_sequence(out->data(), n, s);
     return out;
   }
-  validate_probe(left);
-  auto tmp           = cudf::get_current_device_resource_ref();
-  fjoin::geometry const g = fjoin::geometry_of(n);
+  rowset::validate_probe(_right, left, "Filtered join");
+  rowset::compaction c{n, s};
   fjoin::probe_args a{};
   a.probe          = make_device_table(left);
   a.anti           = anti ? 1 : 0;
   a.null_match     = _null_match ? 1 : 0;
   a.sentinel_match = _sentinel_match ? 1 : 0;
   a.nrows          = n;
-  a.chunk          = g.chunk;
-  a.nwaves         = g.nwaves;
-  rmm::device_buffer mask{static_cast<std::size_t>((n + 63) / 64) * sizeof(uint64_t), s, tmp};
-  rmm::device_buffer counts{static_cast<std::size_t>(g.nwaves + 1) * sizeof(unsigned long long), s, tmp};
-  a.mask   = static_cast<uint64_t*>(mask.data());
-  a.counts = static_cast<unsigned long long*>(counts.data());
+  a.chunk          = c.g.chunk;
+  a.nwaves         = c.g.nwaves;
+  a.mask           = c.mask();
+  a.counts         = c.counts();
   if (_form == fjoin::form::bitmap) {
     a.bm.key   = _build_dev.col[0];
     a.bm.lo    = _lo;
@@ -179,13 +124,7 @@ std::unique_ptr<rmm::device_uvector<size_type>> filtered_join_impl::probe(table_
     a.set.nulls_equal = _nulls_equal == null_equality::EQUAL ? 1 : 0;
     fjoin::launch_set_probe(a, s);
   }
-  auto const total = scan_total(a.counts, g.nwaves, s);  // (the one read-back: sizes the output exactly)
-  auto out         = std::make_unique<rmm::device_uvector<size_type>>(static_cast<std::size_t>(total), s, mr);
-  a.out            = out->data();
-  a.out_capacity   = total;
-  if (total > 0) fjoin::launch_fjoin_compact(a, s);
-  // (no synchronisation: the scratch goes back to the pool in stream order, the caller reads the result on this stream)
-  return out;
+  return std::make_unique<rmm::device_uvector<size_type>>(c.compact_indices(s, mr));
 }
 
 }  // namespace detail

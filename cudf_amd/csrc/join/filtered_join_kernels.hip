@@ -3,16 +3,16 @@
 // left row, and the ordered compaction of those bits into ascending row indices. Replaces the reference's cuco::static_set
 // insert / contains and thrust::copy_if over a counting iterator (cpp/src/join/filtered_join/filtered_join.cu, semi_anti_join).
 #include "filtered_join_impl.hpp"
-#include "set_device.hpp"
 #include "../common/profiler.hpp"
+#include "../common/row_set.hpp"
+#include "../common/row_set_host.hpp"
 
-#include <cudf/utilities/error.hpp>
-
-#include <algorithm>
 #include <mutex>
 
 namespace cudf::detail::fjoin {
 namespace {
+
+using namespace rowset;
 
 constexpr int PROBE_THREADS = 256;   // pass 1 (global bitmap, set) and pass 2: 4 waves per workgroup
 constexpr int LDS_THREADS   = 1024;  // pass 1 from an LDS bitmap: 16 waves share one copy
@@ -48,21 +48,11 @@ __global__ void __launch_bounds__(256) k_set_build_inline(set_args a)
       continue;
     }
     uint64_t const key = normalize_key_bits(load_bits<W>(c, i), c.cls);
-    if (key == SET_EMPTY) {  // (8-byte keys only) the one value a slot cannot hold
+    if (key == EMPTY) {  // (8-byte keys only) the one value a slot cannot hold
       seen_sentinel = true;
       continue;
     }
-    uint64_t s = home_slot(murmur3_32_bits(key, W, 0), a.capacity);
-    while (true) {
-      uint64_t cur = gload(a.slots + s);
-      if (cur == SET_EMPTY) {
-        cur = atomicCAS(reinterpret_cast<unsigned long long*>(a.slots + s), static_cast<unsigned long long>(SET_EMPTY),
-                        static_cast<unsigned long long>(key));
-        if (cur == SET_EMPTY) break;  // inserted
-      }
-      if (cur == key) break;  // a slot changes once, from empty to its key: an equal key is already in the set
-      s = next_slot(s, a.capacity);
-    }
+    claim(a.slots, 1, a.capacity, home_slot(murmur3_32_bits(key, W, 0), a.capacity), key, [&](uint64_t cur) { return cur == key; });
   }
   if (__any(seen_null) && (threadIdx.x & 63) == 0) gstore(a.seen_null, 1);
   if (__any(seen_sentinel) && (threadIdx.x & 63) == 0) gstore(a.seen_sentinel, 1);
@@ -75,71 +65,31 @@ __global__ void __launch_bounds__(256) k_set_build_rows(set_args a)
   bool const eq        = a.nulls_equal != 0;
   for (int64_t i = blockIdx.x * static_cast<int64_t>(blockDim.x) + threadIdx.x; i < n; i += stride) {
     if (!eq && row_has_null(a.build, i)) continue;  // null_equality::UNEQUAL: such a row equals no row
-    uint32_t const h     = row_hash(a.build, i, 0);
-    uint64_t const entry = (static_cast<uint64_t>(h) << 32) | static_cast<uint32_t>(i);
-    uint64_t s           = home_slot(h, a.capacity);
-    while (true) {
-      uint64_t cur = gload(a.slots + s);
-      if (cur == SET_EMPTY) {
-        cur = atomicCAS(reinterpret_cast<unsigned long long*>(a.slots + s), static_cast<unsigned long long>(SET_EMPTY),
-                        static_cast<unsigned long long>(entry));
-        if (cur == SET_EMPTY) break;
-      }
-      if ((cur >> 32) == h && rows_equal(a.build, static_cast<uint32_t>(cur), a.build, i, eq)) break;  // a distinct set
-      s = next_slot(s, a.capacity);
-    }
+    uint32_t const h = row_hash(a.build, i, 0);
+    claim(a.slots, 1, a.capacity, home_slot(h, a.capacity), (static_cast<uint64_t>(h) << 32) | static_cast<uint32_t>(i), [&](uint64_t cur) {
+      return (cur >> 32) == h && rows_equal(a.build, static_cast<uint32_t>(cur), a.build, i, eq);  // a distinct set
+    });
   }
 }
 
 // ------------------------------------------------------------------ pass 1: one bit per left row
-// Wave `wave` tests rows [wave * chunk, + chunk) of the left table, UNROLL x 64 rows at a time: every lane first loads its rows'
-// keys (clamped to the chunk, so that the loads need no branch and stay in flight together), then tests them. The ballot of a
-// 64-row group is its mask word.
+// rowset::probe_chunk over wave `wave`'s chunk of the left table, with p.load(row) and p.test(key, row): a row qualifies when it
+// has a match (semi) or has none (anti).
 template <int UNROLL, typename Probe>
-__device__ __forceinline__ void probe_chunk(probe_args const& a, int64_t wave, Probe const& p)
+__device__ __forceinline__ void probe_wave(probe_args const& a, int64_t wave, Probe const& p)
 {
-  using key_t          = typename Probe::key_t;
-  int const lane       = threadIdx.x & 63;
-  int64_t const begin  = wave * a.chunk;
-  int64_t const end    = a.nrows < begin + a.chunk ? a.nrows : begin + a.chunk;
-  bool const anti      = a.anti != 0;
-  unsigned long long n = 0;
-  for (int64_t r0 = begin; r0 < end; r0 += UNROLL * 64) {
-    key_t k[UNROLL];
-#pragma unroll
-    for (int j = 0; j < UNROLL; ++j) {
-      int64_t const r = r0 + j * 64 + lane;
-      k[j]            = p.load(r < end ? r : end - 1);
-    }
-#pragma unroll
-    for (int j = 0; j < UNROLL; ++j) {
-      int64_t const r = r0 + j * 64 + lane;
-      bool const q    = r < end && (p.test(k[j], r) != anti);
-      uint64_t const m = __ballot(q);
-      if (r0 + j * 64 < end) {
-        if (lane == 0) gstore(a.mask + ((r0 + j * 64) >> 6), m);
-        n += __popcll(m);
-      }
-    }
-  }
-  if (lane == 0 && wave < a.nwaves) gstore(a.counts + wave, n);
+  bool const anti = a.anti != 0;
+  probe_chunk<UNROLL, true>(
+    a, wave, [&](int64_t r) { return p.load(r); },
+    [&](auto const& k, int64_t r) { return p.test(k, r) != anti; });
 }
-
-struct int_key {
-  uint64_t v;
-  bool valid;
-};
 
 template <int W, bool SIGNED, bool LDS>
 struct bitmap_probe {
-  using key_t = int_key;
   probe_args const& a;
   uint32_t const* lds;
-  __device__ int_key load(int64_t r) const
-  {
-    return {load_int<W, SIGNED>(a.probe.col[0], r), col_is_valid(a.probe.col[0], r)};
-  }
-  __device__ bool test(int_key k, int64_t) const
+  __device__ key load(int64_t r) const { return {load_int<W, SIGNED>(a.probe.col[0], r), col_is_valid(a.probe.col[0], r)}; }
+  __device__ bool test(key k, int64_t) const
   {
     if (!k.valid) return a.null_match != 0;
     uint64_t const off = k.v - a.bm.lo;
@@ -153,7 +103,7 @@ template <int W, bool SIGNED>
 __global__ void __launch_bounds__(PROBE_THREADS) k_bitmap_probe(probe_args a)
 {
   int64_t const wave = static_cast<int64_t>(blockIdx.x) * (PROBE_THREADS / 64) + (threadIdx.x >> 6);
-  probe_chunk<8>(a, wave, bitmap_probe<W, SIGNED, false>{a, nullptr});
+  probe_wave<8>(a, wave, bitmap_probe<W, SIGNED, false>{a, nullptr});
 }
 
 template <int W, bool SIGNED>
@@ -166,48 +116,37 @@ __global__ void __launch_bounds__(LDS_THREADS) k_bitmap_probe_lds(probe_args a)
     reinterpret_cast<u32x4*>(s_bits)[u] = gload(reinterpret_cast<u32x4 const*>(a.bm.bits) + u);
   __syncthreads();
   int64_t const wave = static_cast<int64_t>(blockIdx.x) * (LDS_THREADS / 64) + (threadIdx.x >> 6);
-  probe_chunk<8>(a, wave, bitmap_probe<W, SIGNED, true>{a, s_bits});
+  probe_wave<8>(a, wave, bitmap_probe<W, SIGNED, true>{a, s_bits});
 }
 
 template <int W>
 struct set_probe_inline {
-  using key_t = int_key;
   probe_args const& a;
-  __device__ int_key load(int64_t r) const
+  __device__ key load(int64_t r) const
   {
     device_column const& c = a.probe.col[0];
     return {normalize_key_bits(load_bits<W>(c, r), c.cls), col_is_valid(c, r)};
   }
-  __device__ bool test(int_key k, int64_t) const
+  __device__ bool test(key k, int64_t) const
   {
     if (!k.valid) return a.null_match != 0;
-    if (k.v == SET_EMPTY) return a.sentinel_match != 0;
-    uint64_t s = home_slot(murmur3_32_bits(k.v, W, 0), a.set.capacity);
-    while (true) {
-      uint64_t const cur = gload(a.set.slots + s);
-      if (cur == k.v) return true;
-      if (cur == SET_EMPTY) return false;
-      s = next_slot(s, a.set.capacity);
-    }
+    if (k.v == EMPTY) return a.sentinel_match != 0;
+    uint64_t const home = home_slot(murmur3_32_bits(k.v, W, 0), a.set.capacity);
+    return find(a.set.slots, 1, a.set.capacity, home, [&](uint64_t cur) { return cur == k.v; }) != EMPTY;
   }
 };
 
 struct set_probe_rows {
-  struct key_t {};
   probe_args const& a;
-  __device__ key_t load(int64_t) const { return {}; }
-  __device__ bool test(key_t, int64_t r) const
+  __device__ no_key load(int64_t) const { return {}; }
+  __device__ bool test(no_key, int64_t r) const
   {
     bool const eq = a.set.nulls_equal != 0;
     if (!eq && row_has_null(a.probe, r)) return false;
     uint32_t const h = row_hash(a.probe, r, 0);
-    uint64_t s       = home_slot(h, a.set.capacity);
-    while (true) {
-      uint64_t const cur = gload(a.set.slots + s);
-      if (cur == SET_EMPTY) return false;
-      if ((cur >> 32) == h && rows_equal(a.probe, r, a.set.build, static_cast<uint32_t>(cur), eq)) return true;
-      s = next_slot(s, a.set.capacity);
-    }
+    return find(a.set.slots, 1, a.set.capacity, home_slot(h, a.set.capacity), [&](uint64_t cur) {
+             return (cur >> 32) == h && rows_equal(a.probe, r, a.set.build, static_cast<uint32_t>(cur), eq);
+           }) != EMPTY;
   }
 };
 
@@ -215,23 +154,23 @@ template <int W>
 __global__ void __launch_bounds__(PROBE_THREADS) k_set_probe_inline(probe_args a)
 {
   int64_t const wave = static_cast<int64_t>(blockIdx.x) * (PROBE_THREADS / 64) + (threadIdx.x >> 6);
-  probe_chunk<4>(a, wave, set_probe_inline<W>{a});
+  probe_wave<4>(a, wave, set_probe_inline<W>{a});
 }
 
 __global__ void __launch_bounds__(PROBE_THREADS) k_set_probe_rows(probe_args a)
 {
   int64_t const wave = static_cast<int64_t>(blockIdx.x) * (PROBE_THREADS / 64) + (threadIdx.x >> 6);
-  probe_chunk<1>(a, wave, set_probe_rows{a});
+  probe_wave<1>(a, wave, set_probe_rows{a});
 }
 
 // ------------------------------------------------------------------ pass 2: ordered compaction
-// Wave `wave` writes the rows of the set bits of its chunk's mask words at their positions of the output (compact_chunk,
-// set_device.hpp). No atomics; the output is in row order.
-__global__ void __launch_bounds__(PROBE_THREADS) k_compact(probe_args a)
+// Wave `wave` writes the rows of the set bits of its chunk's mask words at their positions of the output (rowset::compact_chunk).
+__global__ void __launch_bounds__(PROBE_THREADS) k_compact(uint64_t const* mask, unsigned long long const* counts, int64_t chunk,
+                                                           int64_t nrows, size_type* out, uint64_t out_capacity)
 {
   int64_t const wave = static_cast<int64_t>(blockIdx.x) * (PROBE_THREADS / 64) + (threadIdx.x >> 6);
-  compact_chunk(a.mask, a.counts, wave, a.chunk, a.nrows, [&](uint64_t o, int64_t row) {
-    if (o < a.out_capacity) gstore(a.out + o, static_cast<size_type>(row));
+  compact_chunk(mask, counts, wave, chunk, nrows, [&](uint64_t o, int64_t row) {
+    if (o < out_capacity) gstore(out + o, static_cast<size_type>(row));
   });
 }
 
@@ -242,23 +181,6 @@ __global__ void __launch_bounds__(256) k_sequence(size_type* out, int64_t n)
     gstore(out + i, static_cast<size_type>(i));
 }
 
-unsigned grid_for(int64_t n)
-{
-  int64_t const blocks = (n + 255) / 256;
-  return static_cast<unsigned>(std::max<int64_t>(1, std::min<int64_t>(blocks, 256 * 16)));
-}
-
-template <typename F>
-void dispatch_int(int width, bool is_signed, F&& f)
-{
-  switch (width) {
-    case 1: return is_signed ? f.template operator()<1, true>() : f.template operator()<1, false>();
-    case 2: return is_signed ? f.template operator()<2, true>() : f.template operator()<2, false>();
-    case 4: return is_signed ? f.template operator()<4, true>() : f.template operator()<4, false>();
-    case 8: return is_signed ? f.template operator()<8, true>() : f.template operator()<8, false>();
-    default: CUDF_FAIL("filtered_join: the bitmap takes 1-, 2-, 4- or 8-byte integer keys");
-  }
-}
 }  // namespace
 
 uint64_t lds_bits_max() { return uint64_t{LDS_BYTES_MAX} * 8; }
@@ -315,13 +237,6 @@ void launch_set_probe(probe_args const& a, hipStream_t stream)
   CUDF_HIP_TRY(hipGetLastError());
 }
 
-void launch_fjoin_compact(probe_args const& a, hipStream_t stream)
-{
-  cudf::detail::prof::scope prof_{"fjoin_compact", stream};
-  hipLaunchKernelGGL(k_compact, dim3(a.nwaves / (PROBE_THREADS / 64)), dim3(PROBE_THREADS), 0, stream, a);
-  CUDF_HIP_TRY(hipGetLastError());
-}
-
 void launch_fjoin_sequence(size_type* out, int64_t n, hipStream_t stream)
 {
   cudf::detail::prof::scope prof_{"fjoin_sequence", stream};
@@ -330,3 +245,12 @@ void launch_fjoin_sequence(size_type* out, int64_t n, hipStream_t stream)
 }
 
 }  // namespace cudf::detail::fjoin
+
+void cudf::detail::rowset::launch_compact_indices(uint64_t const* mask, unsigned long long const* counts, geometry g, int64_t nrows,
+                                                  size_type* out, uint64_t out_capacity, hipStream_t stream)
+{
+  cudf::detail::prof::scope prof_{"fjoin_compact", stream};
+  hipLaunchKernelGGL(fjoin::k_compact, dim3(g.nwaves / (fjoin::PROBE_THREADS / 64)), dim3(fjoin::PROBE_THREADS), 0, stream, mask, counts,
+                     g.chunk, nrows, out, out_capacity);
+  CUDF_HIP_TRY(hipGetLastError());
+}

@@ -7,15 +7,13 @@
 #include "distinct_impl.hpp"
 #include "../common/env.hpp"
 #include "../common/profiler.hpp"
-#include "../join/filtered_join_impl.hpp"
-#include "../join/hash_join_impl.hpp"
+#include "../common/row_set_host.hpp"
 
 #include <cudf/copying.hpp>
 #include <cudf/reduction/distinct_count.hpp>
 #include <cudf/stream_compaction.hpp>
 
 #include <algorithm>
-#include <cmath>
 
 namespace cudf {
 namespace detail {
@@ -30,27 +28,19 @@ struct table_state {
   rmm::device_buffer state, slots, special, counter;
 };
 
-// One integer key column (1, 2, 4 or 8 bytes; timestamps, durations and decimals included) takes the dense form when its valid
-// keys span at most CUDF_AMD_DISTINCT_DENSE_RATIO (2) state words per row and CUDF_AMD_DISTINCT_DENSE_MAX_ENTRIES (2^28: 1 GiB);
-// 1- and 2-byte keys over their type's range. CUDF_AMD_DISTINCT_DENSE=0 sends every key to the hash set.
-bool dense_range(device_column const& c, int64_t rows, uint64_t& lo, uint64_t& range, hipStream_t s)
+// One integer key column takes the dense form (rowset::small_key_range) when its valid keys span at most
+// CUDF_AMD_DISTINCT_DENSE_RATIO (2) state words per row and CUDF_AMD_DISTINCT_DENSE_MAX_ENTRIES (2^28: 1 GiB).
+// CUDF_AMD_DISTINCT_DENSE=0 sends every key to the hash set.
+std::optional<rowset::key_range> dense_range(device_column const& c, int64_t rows, hipStream_t s)
 {
-  if (env_i64("CUDF_AMD_DISTINCT_DENSE", 1) == 0) return false;
-  if (c.cls != CLS_SINT && c.cls != CLS_UINT) return false;
-  if (c.width <= 2) {
-    range = uint64_t{1} << (8 * c.width);
-    lo    = c.cls == CLS_SINT ? static_cast<uint64_t>(-static_cast<int64_t>(range / 2)) : 0;
-    return true;
-  }
+  if (env_i64("CUDF_AMD_DISTINCT_DENSE", 1) == 0) return std::nullopt;
   auto const ratio = static_cast<uint64_t>(std::clamp<int64_t>(env_i64("CUDF_AMD_DISTINCT_DENSE_RATIO", 2), 0, int64_t{1} << 32));
   auto const max_entries =
     static_cast<uint64_t>(std::max<int64_t>(env_i64("CUDF_AMD_DISTINCT_DENSE_MAX_ENTRIES", int64_t{1} << 28), 0));
-  auto const admits = [&](uint64_t r) { return r <= max_entries && r <= ratio * static_cast<uint64_t>(rows); };
   // the range of the first 65,536 rows is part of the whole range: when it already fails, the full pass over the keys is skipped
   constexpr int64_t prefix = 65536;
-  if (rows > 4 * prefix && (!fjoin::valid_key_range(c, prefix, lo, range, s) || !admits(range))) return false;
-  if (!fjoin::valid_key_range(c, rows, lo, range, s)) return false;
-  return admits(range);
+  if (rows > 4 * prefix && !rowset::small_key_range(c, prefix, rows, ratio, max_entries, s)) return std::nullopt;
+  return rowset::small_key_range(c, rows, rows, ratio, max_entries, s);
 }
 
 // Builds the state of `keys` (at least one row and one column). flags: one zeroed byte per row, set for the rows that bypass the
@@ -75,10 +65,10 @@ void build(table_state& t, table_view const& keys, mode m, null_equality nulls, 
   a.counter = static_cast<unsigned long long*>(t.counter.data());
 
   device_column const& c = a.keys.col[0];
-  uint64_t lo = 0, range = 0;
-  if (keys.num_columns() == 1 && dense_range(c, n, lo, range, s)) {
+  if (auto const r = keys.num_columns() == 1 ? dense_range(c, n, s) : std::nullopt) {
+    uint64_t const range = r->range;
     t.dense = true;
-    a.lo    = lo;
+    a.lo    = r->lo;
     a.range = range;
     t.state = rmm::device_buffer{static_cast<std::size_t>(std::max<uint64_t>(range, 1)) * sizeof(uint32_t), s, tmp};
     CUDF_HIP_TRY(hipMemsetAsync(t.state.data(), 0xff, t.state.size(), s));
@@ -90,17 +80,13 @@ void build(table_state& t, table_view const& keys, mode m, null_equality nulls, 
     launch_dense_build(a, t.lds_entries, s);
     return;
   }
-  // the set: rows / (CUDF_AMD_DISTINCT_LOAD_PERCENT (80) / 100) slots, at least rows + 1, counted in 64 bits. Distinct keys fill at most
+  // the set: rowset::set_capacity at load CUDF_AMD_DISTINCT_LOAD_PERCENT (80) / 100. Distinct keys fill at most
   // that share of it, and only when every row is distinct; the slots are initialised and swept in full, so their bytes cost
   // every call ("Distinct rows"). CUDF_AMD_DISTINCT_INLINE=0 keeps {row hash | row} slots for every key.
   double const load = std::clamp(static_cast<double>(env_i64("CUDF_AMD_DISTINCT_LOAD_PERCENT", 80)), 10.0, 95.0) / 100;
-  a.capacity        = static_cast<uint64_t>(std::max(std::ceil(static_cast<double>(n) / load), static_cast<double>(n) + 1));
-  a.inline_key   = keys.num_columns() == 1 && (c.width == 4 || c.width == 8) &&
-                   (c.cls == CLS_SINT || c.cls == CLS_UINT || c.cls == CLS_F32 || c.cls == CLS_F64) &&
-                   env_i64("CUDF_AMD_DISTINCT_INLINE", 1) != 0
-                     ? 1
-                     : 0;
-  // inline keys under a keep rule: 16-byte records {key, state[2]}, all bits set (SET_EMPTY, STATE_EMPTY); otherwise 8-byte slots
+  a.capacity        = rowset::set_capacity(n, load, "distinct: the hash set");
+  a.inline_key      = rowset::inline_key_column(a.keys) && env_i64("CUDF_AMD_DISTINCT_INLINE", 1) != 0 ? 1 : 0;
+  // inline keys under a keep rule: 16-byte records {key, state[2]}, all bits set (rowset::EMPTY, STATE_EMPTY); otherwise 8-byte slots
   a.slot_stride = a.inline_key && m != mode::count ? 2 : 1;
   t.slots = rmm::device_buffer{static_cast<std::size_t>(a.capacity * a.slot_stride) * sizeof(uint64_t), s, tmp};
   CUDF_HIP_TRY(hipMemsetAsync(t.slots.data(), 0xff, t.slots.size(), s));
@@ -144,29 +130,15 @@ std::unique_ptr<column> indices(table_view const& input, duplicate_keep_option k
   mode const m    = mode_of(keep);
   if (n == 0 || input.num_columns() == 0) return empty_indices();
   hipStream_t const s = stream.value();
-  auto tmp            = cudf::get_current_device_resource_ref();
-  rmm::device_buffer flags{static_cast<std::size_t>(n), s, tmp};
+  rmm::device_buffer flags{static_cast<std::size_t>(n), s, cudf::get_current_device_resource_ref()};
   CUDF_HIP_TRY(hipMemsetAsync(flags.data(), 0, flags.size(), s));
   table_state t;
   build(t, input, m, nulls, nans, static_cast<uint8_t*>(flags.data()), stream);
   launch_sweep(t.a, s);
-  rmm::device_buffer mask{static_cast<std::size_t>((n + 63) / 64) * sizeof(uint64_t), s, tmp};  // (every word written by the pack)
-  // the mask -> ascending indices: filtered_join's chunk geometry, scan and ordered compaction
-  fjoin::geometry const g = fjoin::geometry_of(n);
-  rmm::device_buffer counts{static_cast<std::size_t>(g.nwaves + 1) * sizeof(unsigned long long), s, tmp};
-  fjoin::probe_args p{};
-  p.nrows  = n;
-  p.chunk  = g.chunk;
-  p.nwaves = g.nwaves;
-  p.mask   = static_cast<uint64_t*>(mask.data());
-  p.counts = static_cast<unsigned long long*>(counts.data());
-  launch_pack(static_cast<uint8_t const*>(flags.data()), p.mask, n, p.chunk, p.nwaves, p.counts, s);
-  auto const total = scan_total(p.counts, g.nwaves, s);  // (the one read-back: sizes the output exactly)
-  rmm::device_uvector<size_type> out(static_cast<std::size_t>(total), s, mr);
-  p.out          = out.data();
-  p.out_capacity = total;
-  if (total > 0) fjoin::launch_fjoin_compact(p, s);
-  return std::make_unique<column>(std::move(out), rmm::device_buffer{}, 0);
+  // the flag bytes -> mask words and chunk counts (every word written by the pack) -> ascending indices
+  rowset::compaction c{n, s};
+  launch_pack(static_cast<uint8_t const*>(flags.data()), c.mask(), n, c.g.chunk, c.g.nwaves, c.counts(), s);
+  return std::make_unique<column>(c.compact_indices(s, mr), rmm::device_buffer{}, 0);
 }
 
 std::unique_ptr<table> distinct(table_view const& input, std::vector<size_type> const& keys, duplicate_keep_option keep,

@@ -1,25 +1,16 @@
 // SPDX-License-Identifier: Apache-2.0
 // gfx950 kernels of cudf::distinct (distinct_impl.hpp): the dense and set builds that leave one state word per set of equal rows,
-// the sweep of those words into one bit per surviving row, and the per-chunk counts of that mask for filtered_join's ordered
-// compaction. Replaces the reference's cuco::static_set / static_map with a reduction of row indices per key and the copy_if that
+// the sweep of those words into one bit per surviving row, and the per-chunk counts of that mask for the ordered compaction
+// (rowset::compaction). Replaces the reference's cuco::static_set / static_map with a reduction of row indices per key and the copy_if that
 // follows (cpp/src/stream_compaction/distinct_helpers.cu, distinct.cu, stable_distinct.cu; reductions/distinct_count.cu).
 #include "distinct_impl.hpp"
 #include "../common/profiler.hpp"
-#include "../join/filtered_join_impl.hpp"
-#include "../join/set_device.hpp"
-
-#include <cudf/utilities/error.hpp>
-
-#include <algorithm>
+#include "../common/row_set.hpp"
 
 namespace cudf::detail::distinct {
 namespace {
 
-using fjoin::home_slot;
-using fjoin::load_bits;
-using fjoin::load_int;
-using fjoin::next_slot;
-using fjoin::SET_EMPTY;
+using namespace rowset;
 
 constexpr int THREADS     = 256;
 constexpr int LDS_THREADS = 1024;
@@ -188,31 +179,18 @@ __global__ void __launch_bounds__(THREADS) k_set_build_inline(build_args a)
     uint64_t const key  = normalize_key_bits(raw, c.cls);
     nan_seen |= nan;
     bool const bypass   = (active && !valid && !a.nulls_equal) || (nan && !a.nans_equal);
-    bool const sentinel = valid && !bypass && key == SET_EMPTY;  // (8-byte keys only) the one value a slot cannot hold
+    bool const sentinel = valid && !bypass && key == EMPTY;  // (8-byte keys only) the one value a slot cannot hold
     if (valid && !bypass && !sentinel) {
-      uint64_t s    = home_slot(murmur3_32_bits(key, W, 0), a.capacity);
-      bool inserted = false;
-      while (true) {
-        uint64_t cur = gload(a.slots + s * a.slot_stride);
-        if (cur == SET_EMPTY) {
-          cur = atomicCAS(reinterpret_cast<unsigned long long*>(a.slots + s * a.slot_stride), static_cast<unsigned long long>(SET_EMPTY),
-                          static_cast<unsigned long long>(key));
-          if (cur == SET_EMPTY) {
-            inserted = true;
-            break;
-          }
-        }
-        if (cur == key) break;
-        s = next_slot(s, a.capacity);
-      }
+      auto const got = claim(a.slots, a.slot_stride, a.capacity, home_slot(murmur3_32_bits(key, W, 0), a.capacity), key,
+                             [&](uint64_t cur) { return cur == key; });
       if constexpr (MODE == COUNT) {
-        cnt += inserted ? 1u : 0u;
+        cnt += got.inserted ? 1u : 0u;
       } else {
         // the record's two words: st[0] is written once, by the row whose CAS inserted the key (a plain store); st[1] folds the
         // other rows. A row that already sees a better st[0] does nothing (st[0] never changes once written).
-        uint32_t* const st = a.state + s * a.state_stride;
+        uint32_t* const st = a.state + got.slot * a.state_stride;
         uint32_t const v   = encode<MODE>(i);
-        if (inserted) gstore(st, v);
+        if (got.inserted) gstore(st, v);
         else if constexpr (MODE == NONE) {
           if (gload(st + 1) != STATE_MULTI) gstore(st + 1, STATE_MULTI);  // a second row: every store writes the same value
         } else if constexpr (MODE != ANY) {
@@ -249,26 +227,16 @@ __global__ void __launch_bounds__(THREADS) k_set_build_rows(build_args a)
       if (!bypass) {
         uint32_t const h     = row_hash(a.keys, i, 0);
         uint64_t const entry = (static_cast<uint64_t>(h) << 32) | static_cast<uint32_t>(i);
-        uint64_t s           = home_slot(h, a.capacity);
-        while (true) {
-          auto* const p = reinterpret_cast<unsigned long long*>(a.slots + s);
-          uint64_t cur  = gload(a.slots + s);
-          if (cur == SET_EMPTY) {
-            cur = atomicCAS(p, static_cast<unsigned long long>(SET_EMPTY), static_cast<unsigned long long>(entry));
-            if (cur == SET_EMPTY) {
-              if (MODE == COUNT) ++cnt;
-              break;
-            }
-          }
-          if ((cur >> 32) == h && rows_equal(a.keys, static_cast<uint32_t>(cur) & 0x7fffffffu, a.keys, i, eq)) {
-            if constexpr (MODE == FIRST) atomicMin(p, static_cast<unsigned long long>(entry));
-            else if constexpr (MODE == LAST) atomicMax(p, static_cast<unsigned long long>(entry));
-            else if constexpr (MODE == NONE) {
-              if (!(cur & ROW_MULTI)) atomicOr(p, static_cast<unsigned long long>(ROW_MULTI));
-            }
-            break;
-          }
-          s = next_slot(s, a.capacity);
+        auto const got       = claim(a.slots, 1, a.capacity, home_slot(h, a.capacity), entry, [&](uint64_t cur) {
+          return (cur >> 32) == h && rows_equal(a.keys, static_cast<uint32_t>(cur) & 0x7fffffffu, a.keys, i, eq);  // (less ROW_MULTI)
+        });
+        auto* const p        = reinterpret_cast<unsigned long long*>(a.slots + got.slot);
+        if (got.inserted) {
+          if (MODE == COUNT) ++cnt;
+        } else if constexpr (MODE == FIRST) atomicMin(p, static_cast<unsigned long long>(entry));
+        else if constexpr (MODE == LAST) atomicMax(p, static_cast<unsigned long long>(entry));
+        else if constexpr (MODE == NONE) {
+          if (!(got.cur & ROW_MULTI)) atomicOr(p, static_cast<unsigned long long>(ROW_MULTI));
         }
       }
     }
@@ -288,7 +256,7 @@ __global__ void __launch_bounds__(THREADS) k_sweep(build_args a, uint64_t entrie
   for (uint64_t e = static_cast<uint64_t>(blockIdx.x) * blockDim.x + threadIdx.x; e < entries; e += stride) {
     if constexpr (ROW_SLOTS) {
       uint64_t const cur = gload(a.slots + e);
-      if (cur == SET_EMPTY || (MODE == NONE && (cur & ROW_MULTI))) continue;
+      if (cur == EMPTY || (MODE == NONE && (cur & ROW_MULTI))) continue;
       set_bit(a.flags, static_cast<uint32_t>(cur) & 0x7fffffffu);
     } else {
       uint32_t v = gload(a.state + e * a.state_stride);
@@ -337,12 +305,6 @@ __global__ void __launch_bounds__(THREADS) k_pack(uint8_t const* flags, uint64_t
   if (lane == 0) gstore(counts + wave, n);
 }
 
-unsigned grid_for(int64_t n, int threads)
-{
-  int64_t const blocks = (n + threads - 1) / threads;
-  return static_cast<unsigned>(std::max<int64_t>(1, std::min<int64_t>(blocks, 256 * 16)));
-}
-
 template <typename F>
 void dispatch_mode(int32_t m, F&& f)
 {
@@ -356,17 +318,6 @@ void dispatch_mode(int32_t m, F&& f)
   }
 }
 
-template <typename F>
-void dispatch_int(int width, bool is_signed, F&& f)
-{
-  switch (width) {
-    case 1: return is_signed ? f.template operator()<1, true>() : f.template operator()<1, false>();
-    case 2: return is_signed ? f.template operator()<2, true>() : f.template operator()<2, false>();
-    case 4: return is_signed ? f.template operator()<4, true>() : f.template operator()<4, false>();
-    case 8: return is_signed ? f.template operator()<8, true>() : f.template operator()<8, false>();
-    default: CUDF_FAIL("distinct: the dense form takes 1-, 2-, 4- or 8-byte integer keys");
-  }
-}
 }  // namespace
 
 uint64_t lds_entries_max() { return LDS_ENTRIES_MAX; }

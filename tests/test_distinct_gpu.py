@@ -253,6 +253,38 @@ def test_float_keys_each_set_form(G, monkeypatch, form, ty):
                 assert k.get(FORMS[form][1], 0) == 1, k
 
 
+@pytest.mark.parametrize("form", ["set_inline", "set_rows"])
+@pytest.mark.parametrize("ty", ["int64", "uint64"])
+def test_all_ones_key_each_set_form(G, monkeypatch, form, ty):
+    """The 8-byte key whose bits are all ones (int64 -1, uint64 2^64 - 1) is the word of an empty slot: the inline set gives it a
+    state word of its own; in {hash | row} slots it is a key like any other. 1,000 rows with duplicates and a few NULLs, every keep
+    rule and the count."""
+    from oracle.oracle import HostColumn
+    from cudf_amd import reduce
+    from cudf_amd import stream_compaction as SC
+    env, build = FORMS[form]
+    for k, v in env.items():
+        monkeypatch.setenv(k, v)
+    rng = np.random.default_rng(len(form) + len(ty))
+    npt = np.dtype(ty).type
+    data = rng.integers(0, 300, 1000).astype(npt)
+    ones_rows = [0, 5, 333, 640, 999]
+    data[ones_rows] = npt(-1) if ty == "int64" else npt(2**64 - 1)
+    valid = rng.random(1000) >= 0.01
+    valid[ones_rows] = True
+    keys = [HostColumn(data, valid, ty)]
+    t = _table(G, keys)
+    for keep in KEEPS:
+        for ne in (True, False):
+            idx, k = _kernels_of(lambda: _indices(SC.distinct_indices(t, _keep(keep), *_eqs(ne, True))))
+            _check_indices(idx, keys, keep, ne, True)
+            kept = set(ones_rows) & set(idx.tolist())
+            assert {"any": len(kept) == 1, "first": kept == {0}, "last": kept == {999}, "none": not kept}[keep], kept
+            assert k.get(build, 0) == 1 and not any(k.get(o, 0) for o in BUILDS - {build}), k
+    n, k = _kernels_of(lambda: reduce.distinct_count_table(t))
+    assert n == R.distinct_count_table(keys) and k.get(build, 0) == 1 and not k.get("distinct_sweep"), k
+
+
 @pytest.mark.parametrize("types", [("int32", "int8"), ("int64", "float64", "bool"), ("uint16", "float32", "decimal64", "int64")],
                          ids=lambda t: "_".join(t))
 def test_several_keys_with_payload(G, types):

@@ -1,6 +1,6 @@
 """GPU tests of cudf::filtered_join (left semi / anti joins) through the C ABI: the golden vectors (tests/golden/kat_semi_anti_join.json),
 seeded random inputs against the numpy restatement (tests/filtered_join_restatement.py), each build form and probe forced through the
-CUDF_AMD_FJOIN_* settings and proven by the kernels that ran, repeated and concurrent probes, the reference's large-extent case, a
+CUDF_AMD_FJOIN_* settings and proven by the kernels that ran, the all-ones key and a full set at load factor 1, repeated and concurrent probes, the reference's large-extent case, a
 100M x 10M property against torch.isin, and the rejected inputs."""
 import numpy as np
 import pytest
@@ -237,6 +237,59 @@ def test_bitmap_admission(G, monkeypatch):
         (semi, anti), k = _kernels_of(lambda: _both(G, left, right, True))
         assert k.get(built, 0) == 1, k
         assert semi.tolist() == [0, 2, 3] and anti.tolist() == [1]
+
+
+# ---------------------------------------------------------------- the slot walk at its edges
+@pytest.mark.parametrize("present", [True, False], ids=["present", "absent"])
+@pytest.mark.parametrize("ty", ["int64", "uint64"])
+def test_all_ones_key_on_the_hash_set(G, monkeypatch, ty, present):
+    """The 8-byte key whose bits are all ones (int64 -1, uint64 2^64 - 1) is the word of an empty slot: the inline set keeps it in a
+    flag instead. 1,000 rows a side with duplicates and a few NULLs; the key on both sides, or on the probe side only."""
+    from oracle.oracle import HostColumn
+    from cudf_amd.join import FilteredJoin
+    from cudf_amd.types import NullEquality
+    monkeypatch.setenv("CUDF_AMD_FJOIN_DENSE", "0")
+    rng = np.random.default_rng(["int64", "uint64"].index(ty) * 2 + int(present))
+    npt = np.dtype(ty).type
+    ones = npt(-1) if ty == "int64" else npt(2**64 - 1)
+    rdata, ldata = rng.integers(0, 600, 1000).astype(npt), rng.integers(0, 1200, 1000).astype(npt)
+    if present:
+        rdata[[3, 500, 999]] = ones
+    ldata[[0, 17, 64, 511, 999]] = ones
+    lvalid = rng.random(1000) >= 0.01
+    lvalid[0] = True
+    right = [HostColumn(rdata, rng.random(1000) >= 0.01, ty)]
+    left = [HostColumn(ldata, lvalid, ty)]
+    lt = _table(G, left)
+    for eq in (True, False):
+        fj, k = _kernels_of(lambda: FilteredJoin(_table(G, right), NullEquality.EQUAL if eq else NullEquality.UNEQUAL))
+        assert k.get("fjoin_set_build", 0) == 1 and not k.get("fjoin_bitmap_build"), k
+        expect = R.semi_anti(left, right, eq)
+        assert (0 in expect[0].tolist()) == present  # (left row 0 holds the key)
+        for kind in ("semi", "anti"):
+            out, k = _kernels_of(lambda: _indices(getattr(fj, kind + "_join")(lt)))
+            _check(out, expect[kind == "anti"])
+            assert k.get("fjoin_probe_set", 0) == 1 and k.get("fjoin_compact", 0) == 1, k
+
+
+@pytest.mark.parametrize("form", ["inline", "rows"])
+def test_full_set_wraps_and_ends_at_its_one_empty_slot(G, monkeypatch, form):
+    """Load factor 1.0: 257 distinct build keys in 258 slots (rows + 1). The walks run through long clusters, wrap at the last slot,
+    and every absent key ends at the single empty slot. 4,096 probe keys, half of them absent; the inline set (one int64 column)
+    and {hash | row} slots (two columns)."""
+    from oracle.oracle import HostColumn
+    monkeypatch.setenv("CUDF_AMD_FJOIN_DENSE", "0")
+    rng = np.random.default_rng(258 + len(form))
+    pool = rng.choice(1 << 40, 257 + 2048, replace=False).astype(np.int64)
+    build, absent = pool[:257], pool[257:]
+    probe = rng.permutation(np.concatenate([build[rng.integers(0, 257, 2048)], absent]))
+    right, left = [HostColumn(build)], [HostColumn(probe)]
+    if form == "rows":
+        right.append(HostColumn(build ^ 0x5555))
+        left.append(HostColumn(probe ^ 0x5555))
+    (semi, anti), k = _kernels_of(lambda: _compare(G, left, right, False, load_factor=1.0))
+    assert len(semi) == 2048 and len(anti) == 2048
+    assert k.get("fjoin_set_build", 0) == 1 and k.get("fjoin_probe_set", 0) == 2 and k.get("fjoin_compact", 0) == 2, k
 
 
 # ---------------------------------------------------------------- one object, many probes, two streams
