@@ -91,6 +91,15 @@ SYMBOLS = {
                                     C.c_int32, C.c_int32, _P, C.POINTER(_P)]),
     "cudf_amd_distinct_count_column": (C.c_int, [C.POINTER(ColumnView), C.c_int32, C.c_int32, _P, C.POINTER(C.c_int32)]),
     "cudf_amd_distinct_count_table": (C.c_int, [C.POINTER(ColumnView), C.c_int32, C.c_int32, _P, C.POINTER(C.c_int32)]),
+    "cudf_amd_apply_boolean_mask": (C.c_int, [C.POINTER(ColumnView), C.c_int32, C.POINTER(ColumnView), C.c_int32, _P, C.POINTER(_P)]),
+    "cudf_amd_drop_nulls": (C.c_int, [C.POINTER(ColumnView), C.c_int32, C.POINTER(C.c_int32), C.c_int32, C.c_int32, _P,
+                                      C.POINTER(_P)]),
+    "cudf_amd_drop_nans": (C.c_int, [C.POINTER(ColumnView), C.c_int32, C.POINTER(C.c_int32), C.c_int32, C.c_int32, _P,
+                                     C.POINTER(_P)]),
+    "cudf_amd_unique": (C.c_int, [C.POINTER(ColumnView), C.c_int32, C.POINTER(C.c_int32), C.c_int32, C.c_int32, C.c_int32, _P,
+                                  C.POINTER(_P)]),
+    "cudf_amd_unique_count_column": (C.c_int, [C.POINTER(ColumnView), C.c_int32, C.c_int32, _P, C.POINTER(C.c_int32)]),
+    "cudf_amd_unique_count_table": (C.c_int, [C.POINTER(ColumnView), C.c_int32, C.c_int32, _P, C.POINTER(C.c_int32)]),
     "cudf_amd_sorted_order": (C.c_int, [C.POINTER(ColumnView), C.c_int32, C.POINTER(C.c_int32), C.c_int32, C.POINTER(C.c_int32),
                                         C.c_int32, C.c_int32, _P, C.POINTER(_P)]),
     "cudf_amd_sort_by_key": (C.c_int, [C.POINTER(ColumnView), C.c_int32, C.POINTER(ColumnView), C.c_int32, C.POINTER(C.c_int32),

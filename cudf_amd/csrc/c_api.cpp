@@ -10,6 +10,7 @@
 #include <cudf/groupby.hpp>
 #include <cudf/partitioning.hpp>
 #include <cudf/reduction/distinct_count.hpp>
+#include <cudf/reduction/unique_count.hpp>
 #include <cudf/merge.hpp>
 #include <cudf/search.hpp>
 #include <cudf/sorting.hpp>
@@ -654,6 +655,95 @@ cudf_amd_status cudf_amd_distinct_count_table(const cudf_amd_column_view* input,
     cudf::stream_ref const s{as_stream(stream)};
     *out_count = cudf::distinct_count(to_table(input, num_columns),
                                       nulls_equal ? cudf::null_equality::EQUAL : cudf::null_equality::UNEQUAL, s);
+  });
+}
+
+static std::vector<cudf::size_type> keys_of(const int32_t* keys, int32_t num_keys)
+{
+  CUDF_EXPECTS(num_keys >= 0, "num_keys must not be negative", std::invalid_argument);
+  CUDF_EXPECTS(num_keys == 0 || keys != nullptr, "keys must not be NULL", std::invalid_argument);
+  return std::vector<cudf::size_type>(keys, keys + num_keys);
+}
+static void give_table(std::unique_ptr<cudf::table> tbl, cudf_amd_table_t* out_table)
+{
+  auto t     = std::make_unique<cudf_amd_table_s>();
+  t->cols    = tbl->release();
+  *out_table = t.release();
+}
+
+cudf_amd_status cudf_amd_apply_boolean_mask(const cudf_amd_column_view* input, int32_t num_columns, const cudf_amd_column_view* mask,
+                                            int32_t deletion, void* stream, cudf_amd_table_t* out_table)
+{
+  return guarded([&] {
+    *out_table = nullptr;
+    CUDF_EXPECTS(num_columns >= 0, "num_columns must not be negative", std::invalid_argument);
+    CUDF_EXPECTS(mask != nullptr, "mask must not be NULL", std::invalid_argument);
+    cudf::stream_ref const s{as_stream(stream)};
+    auto const in = to_table(input, num_columns);
+    give_table(deletion ? cudf::apply_deletion_mask(in, to_view(*mask), s) : cudf::apply_boolean_mask(in, to_view(*mask), s), out_table);
+  });
+}
+
+cudf_amd_status cudf_amd_drop_nulls(const cudf_amd_column_view* input, int32_t num_columns, const int32_t* keys, int32_t num_keys,
+                                    int32_t keep_threshold, void* stream, cudf_amd_table_t* out_table)
+{
+  return guarded([&] {
+    *out_table = nullptr;
+    CUDF_EXPECTS(num_columns >= 0, "num_columns must not be negative", std::invalid_argument);
+    auto const k = keys_of(keys, num_keys);
+    cudf::stream_ref const s{as_stream(stream)};
+    auto const in = to_table(input, num_columns);
+    give_table(keep_threshold < 0 ? cudf::drop_nulls(in, k, s) : cudf::drop_nulls(in, k, keep_threshold, s), out_table);
+  });
+}
+
+cudf_amd_status cudf_amd_drop_nans(const cudf_amd_column_view* input, int32_t num_columns, const int32_t* keys, int32_t num_keys,
+                                   int32_t keep_threshold, void* stream, cudf_amd_table_t* out_table)
+{
+  return guarded([&] {
+    *out_table = nullptr;
+    CUDF_EXPECTS(num_columns >= 0, "num_columns must not be negative", std::invalid_argument);
+    auto const k = keys_of(keys, num_keys);
+    cudf::stream_ref const s{as_stream(stream)};
+    auto const in = to_table(input, num_columns);
+    give_table(keep_threshold < 0 ? cudf::drop_nans(in, k, s) : cudf::drop_nans(in, k, keep_threshold, s), out_table);
+  });
+}
+
+cudf_amd_status cudf_amd_unique(const cudf_amd_column_view* input, int32_t num_columns, const int32_t* keys, int32_t num_keys,
+                                int32_t keep, int32_t nulls_equal, void* stream, cudf_amd_table_t* out_table)
+{
+  return guarded([&] {
+    *out_table = nullptr;
+    CUDF_EXPECTS(num_columns >= 0, "num_columns must not be negative", std::invalid_argument);
+    auto const k = keys_of(keys, num_keys);
+    cudf::stream_ref const s{as_stream(stream)};
+    give_table(cudf::unique(to_table(input, num_columns), k, keep_of(keep),
+                            nulls_equal ? cudf::null_equality::EQUAL : cudf::null_equality::UNEQUAL, s),
+               out_table);
+  });
+}
+
+cudf_amd_status cudf_amd_unique_count_column(const cudf_amd_column_view* input, int32_t null_handling, int32_t nan_handling,
+                                             void* stream, int32_t* out_count)
+{
+  return guarded([&] {
+    CUDF_EXPECTS(input != nullptr && out_count != nullptr, "input and out_count must not be NULL", std::invalid_argument);
+    cudf::stream_ref const s{as_stream(stream)};
+    *out_count = cudf::unique_count(to_view(*input), null_handling ? cudf::null_policy::INCLUDE : cudf::null_policy::EXCLUDE,
+                                    nan_handling ? cudf::nan_policy::NAN_IS_VALID : cudf::nan_policy::NAN_IS_NULL, s);
+  });
+}
+
+cudf_amd_status cudf_amd_unique_count_table(const cudf_amd_column_view* input, int32_t num_columns, int32_t nulls_equal,
+                                            void* stream, int32_t* out_count)
+{
+  return guarded([&] {
+    CUDF_EXPECTS(out_count != nullptr, "out_count must not be NULL", std::invalid_argument);
+    CUDF_EXPECTS(num_columns >= 0, "num_columns must not be negative", std::invalid_argument);
+    cudf::stream_ref const s{as_stream(stream)};
+    *out_count = cudf::unique_count(to_table(input, num_columns),
+                                    nulls_equal ? cudf::null_equality::EQUAL : cudf::null_equality::UNEQUAL, s);
   });
 }
 

@@ -226,6 +226,28 @@ cudf_amd_status cudf_amd_distinct_count_column(const cudf_amd_column_view* input
 cudf_amd_status cudf_amd_distinct_count_table(const cudf_amd_column_view* input, int32_t num_columns, int32_t nulls_equal,
                                               void* stream, int32_t* out_count);
 
+/* ---- cudf::apply_boolean_mask / apply_deletion_mask / drop_nulls / drop_nans / unique (reference
+ * cpp/include/cudf/stream_compaction.hpp) and cudf::unique_count (reference cpp/include/cudf/reduction/unique_count.hpp): the rows
+ * of `input` that pass a predicate, in input order, every column compacted with the one selection.
+ * cudf_amd_apply_boolean_mask: `mask` is one BOOL8 column of num_rows(input) elements; deletion 0 keeps the rows whose element is
+ * valid and non-zero (apply_boolean_mask), deletion 1 the rows whose element is valid and zero (apply_deletion_mask).
+ * cudf_amd_drop_nulls / cudf_amd_drop_nans: `keys` are indices into `input` (one outside it returns CUDF_AMD_OUT_OF_RANGE); a row
+ * survives when at least keep_threshold of its key fields are valid / not NaN; a negative keep_threshold means all keys.
+ * cudf_amd_unique: keep and nulls_equal as for cudf_amd_distinct; equal rows are expected to be adjacent.
+ * cudf_amd_unique_count_column / _table: arguments as for cudf_amd_distinct_count_column / _table. */
+cudf_amd_status cudf_amd_apply_boolean_mask(const cudf_amd_column_view* input, int32_t num_columns, const cudf_amd_column_view* mask,
+                                            int32_t deletion, void* stream, cudf_amd_table_t* out_table);
+cudf_amd_status cudf_amd_drop_nulls(const cudf_amd_column_view* input, int32_t num_columns, const int32_t* keys, int32_t num_keys,
+                                    int32_t keep_threshold, void* stream, cudf_amd_table_t* out_table);
+cudf_amd_status cudf_amd_drop_nans(const cudf_amd_column_view* input, int32_t num_columns, const int32_t* keys, int32_t num_keys,
+                                   int32_t keep_threshold, void* stream, cudf_amd_table_t* out_table);
+cudf_amd_status cudf_amd_unique(const cudf_amd_column_view* input, int32_t num_columns, const int32_t* keys, int32_t num_keys,
+                                int32_t keep, int32_t nulls_equal, void* stream, cudf_amd_table_t* out_table);
+cudf_amd_status cudf_amd_unique_count_column(const cudf_amd_column_view* input, int32_t null_handling, int32_t nan_handling,
+                                             void* stream, int32_t* out_count);
+cudf_amd_status cudf_amd_unique_count_table(const cudf_amd_column_view* input, int32_t num_columns, int32_t nulls_equal,
+                                            void* stream, int32_t* out_count);
+
 /* ---- cudf::sorted_order / sort / sort_by_key, their stable_ forms and cudf::is_sorted (reference cpp/include/cudf/sorting.hpp).
  * column_order: cudf::order per key column (0 ASCENDING, 1 DESCENDING), num_order entries; null_precedence: cudf::null_order per
  * key column (0 AFTER, 1 BEFORE), num_precedence entries. A length of 0 selects the default (ASCENDING / BEFORE for every
