@@ -106,6 +106,7 @@ SYMBOLS = {
                                        C.c_int32, C.POINTER(C.c_int32), C.c_int32, C.c_int32, _P, C.POINTER(_P)]),
     "cudf_amd_is_sorted": (C.c_int, [C.POINTER(ColumnView), C.c_int32, C.POINTER(C.c_int32), C.c_int32, C.POINTER(C.c_int32),
                                      C.c_int32, _P, C.POINTER(C.c_int32)]),
+    "cudf_amd_rank": (C.c_int, [C.POINTER(ColumnView), C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P, C.POINTER(_P)]),
     "cudf_amd_search_bound": (C.c_int, [C.POINTER(ColumnView), C.c_int32, C.POINTER(ColumnView), C.c_int32, C.POINTER(C.c_int32),
                                         C.c_int32, C.POINTER(C.c_int32), C.c_int32, C.c_int32, _P, C.POINTER(_P)]),
     "cudf_amd_merge": (C.c_int, [C.POINTER(C.POINTER(ColumnView)), C.c_int32, C.c_int32, C.POINTER(C.c_int32), C.c_int32,

@@ -815,6 +815,27 @@ cudf_amd_status cudf_amd_is_sorted(const cudf_amd_column_view* input, int32_t nu
   });
 }
 
+cudf_amd_status cudf_amd_rank(const cudf_amd_column_view* input, int32_t method, int32_t column_order, int32_t null_handling,
+                              int32_t null_precedence, int32_t percentage, void* stream, cudf_amd_table_t* out)
+{
+  return guarded([&] {
+    *out = nullptr;
+    CUDF_EXPECTS(input != nullptr, "input must not be NULL", std::invalid_argument);
+    CUDF_EXPECTS(method >= 0 && method <= 4, "rank: method is no cudf::rank_method");
+    CUDF_EXPECTS(column_order == 0 || column_order == 1, "rank: column_order is no cudf::order");
+    CUDF_EXPECTS(null_handling == 0 || null_handling == 1, "rank: null_handling is no cudf::null_policy");
+    CUDF_EXPECTS(null_precedence == 0 || null_precedence == 1, "rank: null_precedence is no cudf::null_order");
+    CUDF_EXPECTS(percentage == 0 || percentage == 1, "rank: percentage is neither 0 nor 1");
+    cudf::stream_ref const s{as_stream(stream)};
+    auto t = std::make_unique<cudf_amd_table_s>();
+    t->cols.push_back(cudf::rank(to_view(*input), static_cast<cudf::rank_method>(method),
+                                 column_order ? cudf::order::DESCENDING : cudf::order::ASCENDING,
+                                 null_handling ? cudf::null_policy::INCLUDE : cudf::null_policy::EXCLUDE,
+                                 null_precedence ? cudf::null_order::BEFORE : cudf::null_order::AFTER, percentage != 0, s));
+    *out = t.release();
+  });
+}
+
 cudf_amd_status cudf_amd_search_bound(const cudf_amd_column_view* haystack, int32_t num_columns, const cudf_amd_column_view* needles,
                                       int32_t num_needle_columns, const int32_t* column_order, int32_t num_order,
                                       const int32_t* null_precedence, int32_t num_precedence, int32_t upper, void* stream,

@@ -1,7 +1,7 @@
 // SPDX-License-Identifier: Apache-2.0
-// The packed radix words of cudf::sorted_order / is_sorted (include/cudf/sorting.hpp) and of cudf::lower_bound / upper_bound /
+// The packed radix words of cudf::sorted_order / is_sorted / rank (include/cudf/sorting.hpp) and of cudf::lower_bound / upper_bound /
 // merge (search.hpp, merge.hpp): the plan the host makes of a key table (sorting.cpp) and the launchers of the kernels that read
-// it (sorting_kernels.hip, search_merge_kernels.hip).
+// it (sorting_kernels.hip, search_merge_kernels.hip) or its sorted words (rank_kernels.hip).
 //
 // Layout. Each key column is a field of vbits + nbit bits: vbits = 1 for BOOL8, otherwise 8 * width; nbit = 1 if the column has
 // nulls, else 0. The columns are walked from the last to the first and each field is placed above the fields already in the
@@ -19,6 +19,8 @@
 //               come first exactly when (null_precedence == BEFORE) != (order == DESCENDING).
 #pragma once
 #include "../common/device_table.hpp"
+
+#include <cudf/aggregation.hpp>
 
 #include <hip/hip_runtime.h>
 
@@ -72,6 +74,30 @@ void launch_fill_packed_words(plan_word const& w, uint32_t const* payload, uint6
 // *flag (device, zeroed by the caller) becomes non-zero if some row i in [1, n) is lexicographically less than row i - 1; p: the
 // plan in device memory, at least one word
 void launch_is_sorted(packed_plan const* p, int64_t n, uint32_t* flag, hipStream_t s);
+
+// ---- cudf::rank (rank_kernels.hip): the sorted words of ONE column, word i that of sorted position i, and order[i] the row at
+// that position. hi == nullptr: one word; otherwise lo is the value word and hi the null-bit word of a nullable 8-byte column.
+struct rank_words {
+  uint64_t const* lo;
+  uint64_t const* hi;
+};
+constexpr int RANK_TILE = 2048;  // the sorted positions one workgroup ranks at a time (256 threads, 8 each)
+// OUT is int32_t or double. With `percentage` (double only) every rank is divided by `divisor`.
+// out[order[i]] = i + 1
+template <typename OUT>
+void launch_rank_first(uint32_t const* order, OUT* out, int64_t n, bool percentage, double divisor, hipStream_t s);
+// method MIN / MAX / AVERAGE: out[order[i]] = the first position of i's run of equal words + 1 / the last + 1 / their mean
+template <typename OUT>
+void launch_rank_ties(rank_words const& w, uint32_t const* order, OUT* out, int64_t n, rank_method method, bool percentage,
+                      double divisor, hipStream_t s);
+// counts[t] = the runs that start in tile t, for every tile of RANK_TILE positions; *q_heads = those of position q's tile that
+// start at or before q (q < 0: 0)
+void launch_rank_dense_count(rank_words const& w, int64_t n, uint32_t* counts, int64_t q, uint32_t* q_heads, hipStream_t s);
+// out[order[i]] = the runs that start at or before i; tile_base: the exclusive scan of `counts`. The divisor of a percentage is
+// the dense rank of position q, tile_base[q / RANK_TILE] + *q_heads, read on the device.
+template <typename OUT>
+void launch_rank_dense_apply(rank_words const& w, uint32_t const* order, OUT* out, int64_t n, uint32_t const* tile_base,
+                             bool percentage, int64_t q, uint32_t const* q_heads, hipStream_t s);
 
 // ---- rows of two tables (search_merge_kernels.hip). `plans` is device memory that holds two plans of ONE layout, [0] of the
 // haystack and [1] of the needles (launch_store_plans writes them in stream order); nwords is that layout's word count, at least 1.

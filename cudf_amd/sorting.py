@@ -1,10 +1,11 @@
 """pylibcudf.sorting mirror (reference python/pylibcudf/pylibcudf/sorting.pyx: sorted_order, stable_sorted_order, sort, stable_sort,
-sort_by_key, stable_sort_by_key, is_sorted) over cudf::sorted_order and its siblings (include/cudf/sorting.hpp)."""
+sort_by_key, stable_sort_by_key, is_sorted, rank) over cudf::sorted_order and its siblings (include/cudf/sorting.hpp)."""
 import ctypes as C
 
 from . import _lib
+from .aggregation import RankMethod
 from .column import Column, Table, _stream_ptr
-from .types import NullOrder, Order
+from .types import NullOrder, NullPolicy, Order
 
 
 def _orders(column_order, null_precedence):
@@ -66,3 +67,15 @@ def is_sorted(tbl: Table, column_order=None, null_precedence=None, stream=None) 
     _lib.check(_lib.load().cudf_amd_is_sorted(tbl._views(), tbl.num_columns(), *_orders(column_order, null_precedence),
                                               _stream_ptr(stream), C.byref(out)))
     return bool(out.value)
+
+
+def rank(column: Column, method, column_order, null_handling, null_precedence, percentage, stream=None) -> Column:
+    """The rank of every element of `column` in its stable sorted order, from 1: RankMethod FIRST, AVERAGE, MIN, MAX or DENSE
+    among tied rows. FLOAT64 for AVERAGE or with `percentage` (rank / count), else INT32. NullPolicy.EXCLUDE keeps the column's
+    validity; NullPolicy.INCLUDE ranks the nulls and returns no mask."""
+    out = C.c_void_p()
+    view = column._view()
+    _lib.check(_lib.load().cudf_amd_rank(C.byref(view), int(RankMethod(method)), int(Order(column_order)),
+                                         int(NullPolicy(null_handling)), int(NullOrder(null_precedence)), 1 if percentage else 0,
+                                         _stream_ptr(stream), C.byref(out)))
+    return Table._from_handle(out, stream).columns()[0]

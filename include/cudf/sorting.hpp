@@ -1,8 +1,8 @@
 // SPDX-License-Identifier: Apache-2.0
-// cudf::sorted_order, sort, sort_by_key, their stable_ forms and is_sorted: the lexicographic order of the rows of a table.
-// Signatures follow reference cpp/include/cudf/sorting.hpp (sorted_order, stable_sorted_order, is_sorted, sort, stable_sort,
-// sort_by_key, stable_sort_by_key); the stream and memory-resource types are this library's, as in stream_compaction.hpp.
-// rank, top_k and the segmented sorts are not served.
+// cudf::sorted_order, sort, sort_by_key, their stable_ forms and is_sorted: the lexicographic order of the rows of a table; and
+// cudf::rank: the rank of every element of a column. Signatures follow reference cpp/include/cudf/sorting.hpp (sorted_order,
+// stable_sorted_order, is_sorted, sort, stable_sort, sort_by_key, stable_sort_by_key, rank); the stream and memory-resource types
+// are this library's, as in stream_compaction.hpp. top_k and the segmented sorts are not served.
 //
 // Contract:
 //  - Rows compare column by column, the first column most significant. Within a column -0 equals +0, every NaN is one value
@@ -22,8 +22,28 @@
 //  - cudf::logic_error: a non-empty column_order or null_precedence whose size differs from the number of key columns;
 //    values.num_rows() != keys.num_rows(); key tables beyond the device tables' limits (more than 16 columns, a column that is not
 //    fixed-width), as the joins and distinct throw.
-// The radix words and the pass arithmetic: DESIGN.md section 4, "Sorting".
+//
+// rank (reference sorting.hpp:165-230, cpp/src/sort/rank.cu:253-353):
+//  - Ranks start at 1 and follow the stable sorted order of the column under (column_order, null_precedence). Rows tie when they
+//    compare equal above: NaNs tie, -0 ties with +0, and all nulls tie with each other.
+//  - FIRST: the position in the stable order + 1. MIN / MAX: the first / last position of the row's run of tied rows + 1.
+//    AVERAGE: MIN + (run length - 1) / 2.0. DENSE: the number of runs up to and including the row's.
+//    input {3, 4, 5, 4, 1, 2}: FIRST {3, 4, 6, 5, 1, 2}, AVERAGE {3, 4.5, 6, 4.5, 1, 2}, MIN {3, 4, 6, 4, 1, 2},
+//    MAX {3, 5, 6, 5, 1, 2}, DENSE {3, 4, 5, 4, 1, 2}.
+//  - The result is FLOAT64 when method == AVERAGE or `percentage` is set, else INT32; an empty input gives an empty column of it.
+//  - null_policy::INCLUDE: nulls are ranked like any value, and the result has no mask. null_policy::EXCLUDE: the result carries
+//    a copy of the input's validity (from bit 0, whatever the input's offset) and its null count, and the values under a null are
+//    unspecified; an input without a mask gives a result without one.
+//  - percentage: every rank is divided, in double, by count = size (INCLUDE) or size - null_count (EXCLUDE); for DENSE by the
+//    dense rank of sorted position count - 1 instead.
+//  - EXCLUDE is meant for nulls sorted last (ASCENDING with AFTER, DESCENDING with BEFORE). EXCLUDE with nulls sorted first on a
+//    column that has nulls is undefined in the reference (sorting.hpp:204-206). Here the same formulas run unchanged, so the nulls
+//    take the first ranks and a percentage still divides by the count of valid rows; nothing throws, and the values are not part
+//    of the contract.
+//  - cudf::logic_error: a column that is not fixed-width of at most 8 bytes, as sorted_order throws.
+// The radix words and the pass arithmetic: DESIGN.md section 4, "Sorting"; the rank pass: "Ranking".
 #pragma once
+#include <cudf/aggregation.hpp>
 #include <cudf/column/column.hpp>
 #include <cudf/table/table.hpp>
 #include <cudf/table/table_view.hpp>
@@ -65,5 +85,9 @@ std::unique_ptr<table> stable_sort_by_key(table_view const& values, table_view c
                                           std::vector<null_order> const& null_precedence = {},
                                           stream_ref stream                              = get_default_stream(),
                                           rmm::device_async_resource_ref mr              = get_current_device_resource_ref());
+
+std::unique_ptr<column> rank(column_view const& input, rank_method method, order column_order, null_policy null_handling,
+                             null_order null_precedence, bool percentage, stream_ref stream = get_default_stream(),
+                             rmm::device_async_resource_ref mr = get_current_device_resource_ref());
 
 }  // namespace cudf

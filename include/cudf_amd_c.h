@@ -268,6 +268,15 @@ cudf_amd_status cudf_amd_is_sorted(const cudf_amd_column_view* input, int32_t nu
                                    int32_t num_order, const int32_t* null_precedence, int32_t num_precedence, void* stream,
                                    int32_t* out);
 
+/* ---- cudf::rank (reference cpp/include/cudf/sorting.hpp:165-230): the rank of every element of ONE column.
+ * method: cudf::rank_method (0 FIRST, 1 AVERAGE, 2 MIN, 3 MAX, 4 DENSE); column_order (0 ASCENDING, 1 DESCENDING) and
+ * null_precedence (0 AFTER, 1 BEFORE) as for cudf_amd_sorted_order; null_handling: cudf::null_policy (0 EXCLUDE, 1 INCLUDE);
+ * percentage: 0 = the rank, 1 = the rank divided by the count. A value outside its enum returns CUDF_AMD_LOGIC_ERROR.
+ * out = table of ONE column of the input's row count: FLOAT64 for AVERAGE or a percentage, else INT32; under EXCLUDE it carries
+ * the validity of the input. */
+cudf_amd_status cudf_amd_rank(const cudf_amd_column_view* input, int32_t method, int32_t column_order, int32_t null_handling,
+                              int32_t null_precedence, int32_t percentage, void* stream, cudf_amd_table_t* out);
+
 /* ---- cudf::lower_bound / upper_bound (reference cpp/include/cudf/search.hpp) and cudf::merge (cpp/include/cudf/merge.hpp).
  * column_order / null_precedence are encoded as for cudf_amd_sorted_order.
  * cudf_amd_search_bound: upper = 0: lower_bound, 1: upper_bound. out = table of ONE INT32 column of the needles' row count: the
